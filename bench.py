@@ -4,20 +4,28 @@
 
 A step is one frame batch: every (PU, reference picture) sub-pel job of one synthetic 1080p
 P-frame (510 CTUs x 423 calls x 4 references = 862,920 jobs, SURVEY.md §8(d) mix) through
-EMI step -> FracDIF -> NN_pred -> xMotionEstimation tail.  `value` times the steps with their
-inputs already resident in HBM (the task's measurement contract): per step the frame's pictures and
+EMI step -> FracDIF -> NN_pred -> xMotionEstimation tail.  `resident` times the steps with their
+inputs already resident in HBM: per step the frame's pictures and
 lambdas are bound, configs[3]'s bi-pred keys are built on the device, and the batch refines the
 frame's jobs into a device result buffer.  With N ranks (torchrun, one GPU each) rank r replays
 frames r, r+N, ... (weak scaling); each reconstruction is uploaded by one rank and sent (RCCL
 point-to-point) to the ranks whose frames reference it, and the NN carried state is chained across
 ranks at the end of the timed region (all_gather of 12 words per frame + a device re-run of each
-frame's carried-state prefix).  `pcie_inclusive` reports SURVEY.md §8(d)'s wider timing of the same
+frame's carried-state prefix).  `value` (`pcie_inclusive`) is SURVEY.md §8(d)'s wider timing of the same
 steps: per step the jobs (32 B each), the frame's original and one reconstructed reference go over
 PCIe from pinned host memory and the 16-byte fme_mv_result per job comes back
 (nnfme.pipeline.FrameReplay: two steps in flight on separate copy / compute streams); the parity
 leg checks that pass's first timed step against oracle/_ref.
 
-Prints one JSON line (rank 0).  `cpu_baseline` times oracle/_ref (the reference's own
+A plain run sets up, warms up, times the steps of that PCIe-inclusive pass and prints one JSON
+line (rank 0): `value`, and `ms_per_step`, the wall milliseconds of one timed step.
+`--dump-outputs DIR` writes the last timed step's results, as its caller receives them, to
+DIR/<field>.npy (same arguments, same inputs: two builds can be compared output for output).
+Everything below runs only with `--full`: the CPU baselines, the parity leg, the HBM-resident
+pass (`resident`) with the roofline its profiled batches give, and the motion-compensation,
+single-PU, integer-search and predInterSearch legs.
+
+`cpu_baseline` times oracle/_ref (the reference's own
 TLibCommon primitives driven in TEncSearch order, compiled -O2 like the reference build) on
 one host core (HM is single-threaded) over a bounded sample of the same job mix;
 `cpu_baseline_all_cores` runs one job stream per host core.  Both run
@@ -661,11 +669,69 @@ def write_timeline(path, rep, k0, k1, elapsed_s):
                     sum(r["d1"] - r["d0"] for r in rows) / len(rows)))
 
 
+DUMP_LIMIT = 64 << 20   # bytes of all dumped arrays together
+
+
+def dump_outputs(path, rows, rank=0, world=1):
+    """--dump-outputs: one step's fme_mv_result rows, a field per file (<field>.npy, with a
+    rank<r>_ prefix when sharded), in job order.  float32 holds the 16-bit and 8-bit fields
+    exactly, cost and bits (uint32) go to float64.  Rows beyond the size limit: a fixed, seeded
+    sample of the jobs, their indices beside them in sample_index.npy."""
+    from nnfme.abi import MV_FIELDS
+    os.makedirs(path, exist_ok=True)
+    dts = {f: np.float64 if rows.dtype[f].itemsize > 2 else np.float32 for f in MV_FIELDS}
+    per_row = sum(np.dtype(d).itemsize for d in dts.values()) + 8
+    pre = f"rank{rank}_" if world > 1 else ""
+    if len(rows) * per_row > DUMP_LIMIT:
+        idx = np.sort(np.random.default_rng(12345).choice(len(rows), DUMP_LIMIT // per_row, replace=False))
+        rows = rows[idx]
+        np.save(os.path.join(path, pre + "sample_index.npy"), idx.astype(np.float64))
+    for f, d in dts.items():
+        np.save(os.path.join(path, pre + f + ".npy"), rows[f].astype(d))
+
+
 def frame_lambda(wl, f):
     """Lambda of frame f: lowdelay_P by POC % 4 (cfg Frame1-4), random access by GOP-8 entry."""
     if wl["gop"] == "ra":
         return synth.ra_lambda(wl["QP"], f % 8)
     return synth.LDP_LAMBDA[wl["QP"]][(f + 1) % 4]
+
+
+def search_roofline(ctx, jobs, tm, nb, bd, workload):
+    """The main search phase of a batch (module docstring) from the mean kernel times `tm` of `nb`
+    profiled batches: the reference's integer ops per second over the VALU peak, with the HBM roof
+    of the same phase as the `hbm` entry."""
+    small_jobs = jobs[main_kernel_mask(ctx, jobs)]
+    bytes_small = algorithmic_bytes(small_jobs, 2 if bd > 8 else 1)
+    small_s = tm["search_main"] / 1e3
+    ops_small = algorithmic_ops(small_jobs)
+    valu = ops_small / small_s / 1e12
+    gbs = bytes_small / small_s / 1e9
+    traffic, traffic_src = read_pmc_traffic(workload)
+    return {
+        "bound": "valu",
+        "achieved": valu,
+        "peak": VALU_PEAK_TOPS,
+        "unit": "Tops/s (int32 VALU lane-ops)",
+        "frac": valu / VALU_PEAK_TOPS,
+        "traffic": traffic,
+        "kernel": "main search phase: fme::k_search_lane (EMI + FracDIF, every PU shape, one "
+                  "persistent launch per batch)" if bd == 8 else
+                  "main search phase at bit depth 10: fme::k_search_lane10 (EMI + FracDIF on int16 samples, "
+                  "one lane per 4x8 / 4x4 unit, every PU shape, one persistent launch per batch)",
+        "kernel_jobs": int(len(small_jobs)),
+        "algorithmic_ops_per_launch": ops_small,
+        "algorithmic_bytes_per_launch": bytes_small,
+        "kernel_ms": tm["search_main"],
+        "profiled_batches": nb,
+        "note": "integer-VALU bound (~97 reference int ops per algorithmic byte, SURVEY.md §8(d)); "
+                "achieved counts the reference's arithmetic, not the instructions issued",
+        "traffic_source": traffic_src,
+        "batch_kernel_ms": tm,
+        "hbm": {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": gbs / HBM_PEAK_GBS,
+                "traffic_frac_of_algorithmic": (traffic / bytes_small) if traffic else None},
+    }
 
 
 def nn_tail_roofline(wl, tm, n):
@@ -697,6 +763,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baselines, the parity leg against oracle/_ref, the "
+                         "HBM-resident pass with its roofline, and the motion-compensation, single-PU, "
+                         "predInterSearch and integer-search legs (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results (what the timed path hands its caller) as "
+                         "DIR/<field>.npy after the timed steps")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample length")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-mc", action="store_true", help="skip the motion-compensation leg")
@@ -739,6 +812,14 @@ def main():
                     help="results download of step k: once step k+1's search runs (deferred) or right after "
                          "step k (immediate); default: the workload's measured choice (DESIGN.md section 5)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the headline
+        args.no_cpu_baseline = args.no_mc = args.no_tz = args.no_pi = True
+        args.parity_seconds = 0.0
+    # the HBM-resident pass (and the search roofline its profiled batches give): a run of its own
+    # beside the headline, except under --no-pcie, where it is the timed pass
+    do_resident = args.full or args.no_pcie
     crash = None
     if os.environ.get("FME_CRASH_TRACE"):   # diagnostic: native stack of a fault (tools/probes/crash_trace.c)
         import ctypes
@@ -900,6 +981,8 @@ def main():
         rep.check_status(args.warmup)   # no timed step may have been rejected on the device
         if args.timeline:
             write_timeline(args.timeline, rep, args.warmup, steps_total, elapsed_pcie)
+        if args.dump_outputs:   # the last timed step's downloaded rows: what a caller of this path receives
+            dump_outputs(args.dump_outputs, rep.results(steps_total - 1), rank, world)
         snap = rep.results(args.warmup).copy() if args.parity_seconds > 0 else None
         value_pcie = world * n * args.steps / elapsed_pcie
     host_ms = np.asarray(rep.host_ms, dtype=np.float64)
@@ -918,62 +1001,67 @@ def main():
     # left there; per step: bind, device-built keys (configs[3]), refine; the NN-state chain fix-up
     # on the device when sharded.  At one rank its timed steps start from the PCIe pass's first NN
     # state, so every step's results must equal the PCIe pass's bit for bit (checked below). ----
-    rep.resident_outputs(0, steps_total)
-    prefix = rep.last_prefix if world > 1 else 0
-    for s in range(args.warmup):
-        rep.issue_resident(s)
-    if state0 is not None:
-        ctx.nn_set_state(state0)   # stream-ordered: applied before the first timed batch
-    torch.cuda.synchronize(dev)
-    ctx.set_profiling(True)
-    ctx.accumulated_timings(reset=True)
-    if world > 1:
-        dist.barrier()
-    gc.collect()
-    gc.disable()
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for s in range(args.warmup, steps_total):
-        rep.issue_resident(s)
-    fixed = rep.finish_resident(args.warmup, steps_total, prefix)
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    elapsed = max_over_ranks(time.perf_counter() - t0, dev, world, args.dist_backend)
-    gc.enable()
-    nb, acc = ctx.accumulated_timings(reset=True)
-    ctx.set_profiling(False)
-    tm = {k: v / max(nb, 1) for k, v in acc.items()}
-    value_res = world * n * args.steps / elapsed
-    from nnfme.abi import RES_REJECTED
-    res_vs_pcie = None
-    if not args.no_pcie:
-        diff_steps = []
+    resident = tm = None
+    nb = fixed = 0
+    if do_resident:
+        rep.resident_outputs(0, steps_total)
+        prefix = rep.last_prefix if world > 1 else 0
+        for s in range(args.warmup):
+            rep.issue_resident(s)
+        if state0 is not None:
+            ctx.nn_set_state(state0)   # stream-ordered: applied before the first timed batch
+        torch.cuda.synchronize(dev)
+        ctx.set_profiling(True)
+        ctx.accumulated_timings(reset=True)
+        if world > 1:
+            dist.barrier()
+        gc.collect()
+        gc.disable()
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
         for s in range(args.warmup, steps_total):
-            got = rep.r_out[s].cpu().numpy().view(MV_RESULT_DTYPE)
-            if not np.array_equal(got, rep.results(s)):
-                diff_steps.append(s)
-        res_vs_pcie = {"steps_compared": args.steps, "steps_differing": diff_steps,
-                       "equal": not diff_steps, "rank": rank,
-                       "how": "every timed step's 16-byte records of the resident pass against the PCIe pass's "
-                              "downloaded rows, same NN start state" + (" (after the carried-state fix-up)"
-                                                                         if world > 1 else "")}
-        if diff_steps:
-            raise RuntimeError(f"resident pass differs from the PCIe pass on steps {diff_steps}")
-    else:
-        last = rep.r_out[steps_total - 1].cpu().numpy().view(MV_RESULT_DTYPE)
-        if np.any(last["status"] & RES_REJECTED):
-            raise RuntimeError("a resident step's batch was rejected on the device")
+            rep.issue_resident(s)
+        fixed = rep.finish_resident(args.warmup, steps_total, prefix)
+        torch.cuda.synchronize(dev)
+        if world > 1:
+            dist.barrier()
+        elapsed = max_over_ranks(time.perf_counter() - t0, dev, world, args.dist_backend)
+        gc.enable()
+        nb, acc = ctx.accumulated_timings(reset=True)
+        ctx.set_profiling(False)
+        tm = {k: v / max(nb, 1) for k, v in acc.items()}
+        value_res = world * n * args.steps / elapsed
+        from nnfme.abi import RES_REJECTED
+        res_vs_pcie = None
+        if not args.no_pcie:
+            diff_steps = []
+            for s in range(args.warmup, steps_total):
+                got = rep.r_out[s].cpu().numpy().view(MV_RESULT_DTYPE)
+                if not np.array_equal(got, rep.results(s)):
+                    diff_steps.append(s)
+            res_vs_pcie = {"steps_compared": args.steps, "steps_differing": diff_steps,
+                           "equal": not diff_steps, "rank": rank,
+                           "how": "every timed step's 16-byte records of the resident pass against the PCIe pass's "
+                                  "downloaded rows, same NN start state" + (" (after the carried-state fix-up)"
+                                                                             if world > 1 else "")}
+            if diff_steps:
+                raise RuntimeError(f"resident pass differs from the PCIe pass on steps {diff_steps}")
+        else:
+            last = rep.r_out[steps_total - 1].cpu().numpy().view(MV_RESULT_DTYPE)
+            if np.any(last["status"] & RES_REJECTED):
+                raise RuntimeError("a resident step's batch was rejected on the device")
+            if args.dump_outputs:   # --no-pcie: the resident pass is the timed path
+                dump_outputs(args.dump_outputs, last, rank, world)
+        resident = {"value": value_res, "unit": "PU/s", "ms_per_step": elapsed / args.steps * 1e3,
+                    "timed": "per step, inputs resident in HBM: bind the step's pictures and lambdas, build its "
+                             "bi-pred keys on the device (configs[3]), refine the frame's jobs into a device result "
+                             "buffer" + ("; NN-state chain fix-up on the device included" if world > 1 else ""),
+                    **({"of_resident_pcie": value_pcie / value_res} if value_pcie else {}),
+                    **({"equals_pcie_pass": res_vs_pcie} if res_vs_pcie else {})}
     if args.no_pcie:
         value, ms_step, value_kind = value_res, elapsed / args.steps * 1e3, "resident (--no-pcie profiling run)"
     else:
         value, ms_step, value_kind = value_pcie, elapsed_pcie / args.steps * 1e3, "pcie_inclusive (SURVEY.md §8(d))"
-    resident = {"value": value_res, "unit": "PU/s", "ms_per_step": elapsed / args.steps * 1e3,
-                "timed": "per step, inputs resident in HBM: bind the step's pictures and lambdas, build its bi-pred "
-                         "keys on the device (configs[3]), refine the frame's jobs into a device result buffer"
-                         + ("; NN-state chain fix-up on the device included" if world > 1 else ""),
-                **({"of_resident_pcie": value_pcie / value_res} if value_pcie else {}),
-                **({"equals_pcie_pass": res_vs_pcie} if res_vs_pcie else {})}
     d2h = n * MV_RESULT_DTYPE.itemsize
     pcie = None if args.no_pcie else {
         "timed": "from the first H2D of job descriptors to the last D2H of results (SURVEY.md §8(d)): per step H2D "
@@ -1016,14 +1104,6 @@ def main():
                     cpu_seconds=0.0 if args.no_cpu_baseline else 6.0, bd=BD)
 
     if rank == 0:
-        gj = rep.jobs
-        small_jobs = gj[main_kernel_mask(ctx, gj)]
-        bytes_small = algorithmic_bytes(small_jobs, 2 if BD > 8 else 1)
-        small_s = tm["search_main"] / 1e3
-        ops_small = algorithmic_ops(small_jobs)
-        valu = ops_small / small_s / 1e12
-        gbs = bytes_small / small_s / 1e9
-        traffic, traffic_src = read_pmc_traffic(args.workload)
         out = {
             "metric": METRIC,
             "value": value,
@@ -1057,33 +1137,11 @@ def main():
                        "dist_backend": dist.get_backend() if dist.is_initialized() else None,
                        "pg_world_size": dist.get_world_size() if dist.is_initialized() else 1,
                        "timed": (pcie or resident)["timed"]},
-            "roofline": {
-                "bound": "valu",
-                "achieved": valu,
-                "peak": VALU_PEAK_TOPS,
-                "unit": "Tops/s (int32 VALU lane-ops)",
-                "frac": valu / VALU_PEAK_TOPS,
-                "traffic": traffic,
-                "kernel": "main search phase: fme::k_search_lane (EMI + FracDIF, every PU shape, one "
-                          "persistent launch per batch)" if BD == 8 else
-                          "main search phase at bit depth 10: fme::k_search_lane10 (EMI + FracDIF on int16 samples, "
-                          "one lane per 4x8 / 4x4 unit, every PU shape, one persistent launch per batch)",
-                "kernel_jobs": int(len(small_jobs)),
-                "algorithmic_ops_per_launch": ops_small,
-                "algorithmic_bytes_per_launch": bytes_small,
-                "kernel_ms": tm["search_main"],
-                "profiled_batches": nb,
-                "note": "integer-VALU bound (~97 reference int ops per algorithmic byte, SURVEY.md §8(d)); "
-                        "achieved counts the reference's arithmetic, not the instructions issued",
-                "traffic_source": traffic_src,
-                "batch_kernel_ms": tm,
-                "hbm": {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": gbs / HBM_PEAK_GBS,
-                        "traffic_frac_of_algorithmic": (traffic / bytes_small) if traffic else None},
-            },
         }
-        if NN == 2:
-            out["nn_tail_roofline"] = nn_tail_roofline(wl, tm, n)
+        if tm is not None:   # from the resident pass's profiled batches
+            out["roofline"] = search_roofline(ctx, rep.jobs, tm, nb, BD, args.workload)
+            if NN == 2:
+                out["nn_tail_roofline"] = nn_tail_roofline(wl, tm, n)
         out.update(cpu)
         if "cpu_baseline" in cpu:
             out["speedup_vs_cpu_1core"] = value / cpu["cpu_baseline"]["value"]
@@ -1091,11 +1149,14 @@ def main():
             out["speedup_vs_cpu_all_cores"] = value / cpu["cpu_baseline_all_cores"]["value"]
         if pcie:
             out["pcie_inclusive"] = pcie
-        out["resident"] = resident
+        if resident:
+            out["resident"] = resident
         if parity:
             out["parity"] = parity
-        if world > 1:
+        if world > 1 and resident:
             out["nn_state_fixup_jobs_rank0"] = int(fixed)
+        if args.dump_outputs:
+            out["dump_outputs"] = args.dump_outputs
         if mc:
             out["motion_compensation"] = mc
         if single:

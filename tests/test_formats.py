@@ -11,12 +11,13 @@ import os
 import numpy as np
 import pytest
 
-from conftest import golden_cases, load_golden
+from conftest import GOLDEN, golden_cases, load_golden
 from nnfme import dataset, weights
 from nnfme.abi import JOB_DTYPE
 from oracle import Oracle
 
-REF_DL = "/root/reference/DL"
+# the reference's DL/blowing/<qp>/ CSV directories and DL/models/ checkpoints, stored as fixtures
+REF_DL = os.path.join(GOLDEN, "dl")
 
 
 def _oracle(g):
@@ -137,7 +138,6 @@ def test_state_dict_round_trip(tmp_path):
     assert np.array_equal(weights.load_checkpoint(str(f), t["mean"], t["stdev"]), p)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DL), reason="reference DL/ directory not present")
 @pytest.mark.parametrize("qp", [22, 27, 32, 37])
 def test_reference_weight_files_load_to_the_shipped_sets(qp):
     """The reference's CSV directory and its trained checkpoint both load to the weight set

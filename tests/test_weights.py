@@ -3,9 +3,11 @@ import os
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
 from nnfme import weights
 
-REF = "/root/reference/DL/blowing"
+# the reference's per-QP weight CSV directories (DL/blowing/<qp>/), stored as fixtures
+REF = os.path.join(GOLDEN, "dl", "blowing")
 
 
 @pytest.mark.parametrize("qp", [22, 27, 32, 37])
@@ -22,7 +24,6 @@ def test_weight_set_selection_follows_tencsearch_init():
     assert [weights.weight_set_for_qp(q) for q in (22, 27, 32, 37, 30, 0)] == [22, 27, 32, 37, 22, 22]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference CSVs not present")
 @pytest.mark.parametrize("qp", [22, 27, 32, 37])
 def test_weight_blob_equals_reference_csv(qp):
     import re

@@ -3,7 +3,7 @@ import glob
 import json
 import sys
 
-for f in sorted(glob.glob((sys.argv[1] if len(sys.argv) > 1 else "gpurun_out") + "/*.log")):
+for f in sorted(glob.glob((sys.argv[1] if len(sys.argv) > 1 else "bench_out") + "/*.log")):
     line = None
     for ln in open(f, errors="replace"):
         if ln.startswith("{") and '"metric"' in ln:

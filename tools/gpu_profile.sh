@@ -16,7 +16,7 @@ run() {  # name, timeout, command...
   tail -2 "$O/$name.log" | cut -c1-300
   if [ $rc -ne 0 ]; then echo "== $name FAILED rc=$rc"; tail -30 "$O/$name.log"; exit $rc; fi
 }
-B="python bench.py --no-cpu-baseline --no-pi --no-tz --no-mc"
+B="python bench.py --full --no-cpu-baseline --no-pi --no-tz --no-mc"
 P="python3 bench.py --no-cpu-baseline --no-pi --no-tz --no-mc --no-pcie --parity-seconds 0"   # profiled: kernels alone
 if [ "${PROF:-1}" = 1 ]; then
   run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- $P --steps 10 --warmup 2
@@ -34,7 +34,7 @@ if [ "${PROF:-1}" = 1 ]; then
   fi
 fi
 if [ "${WORKLOADS:-1}" = 1 ]; then
-  run bench_c1 300 python bench.py --workload c1 --no-pi --no-tz --no-mc --cpu-seconds 12 --cpu-cores -1
+  run bench_c1 300 python bench.py --full --workload c1 --no-pi --no-tz --no-mc --cpu-seconds 12 --cpu-cores -1
   for w in c2 c3_qp27 c3_qp32 c3_qp37 c3_qp22_main10 c4 c5 c5_exact c5_b4x40; do
     run bench_$w 300 $B --workload $w
   done

@@ -6,10 +6,11 @@
 #   trace  rocprofv3 kernel trace of the headline bench, steady-launch stats (tools/steady_stats.py)
 #   sq     SQ instruction / wait counters of the batch kernels (two passes)
 #   pmc    FETCH_SIZE / WRITE_SIZE passes -> pmc_traffic.json
-# Output under gpurun_out/$TAG.  Each step under its own time limit; the first failure ends the call.
+# Output under $OUT/$TAG.  Each step under its own time limit; the first failure ends the call.
 set -o pipefail
+OUT=${OUT:-bench_out}   # logs and profiler output
 TAG=${TAG:-r04}
-O=gpurun_out/$TAG
+O=$OUT/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 run() {  # name, timeout, command...
@@ -20,7 +21,7 @@ run() {  # name, timeout, command...
   tail -3 "$O/$name.log" | cut -c1-600
   if [ $rc -ne 0 ]; then echo "== $name FAILED rc=$rc"; tail -40 "$O/$name.log"; exit $rc; fi
 }
-B="python bench.py --no-cpu-baseline --no-pi --no-tz --no-mc ${BENCH_ARGS:-}"
+B="python bench.py --full --no-cpu-baseline --no-pi --no-tz --no-mc ${BENCH_ARGS:-}"
 for s in ${STEPS:-bench trace}; do
   case $s in
     tests) run tests 400 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_async.py tests/test_gpu_dist.py \

@@ -1,18 +1,19 @@
 #!/bin/bash
 # Round-6 GPU pass: steps named on the command line, each under its own time limit, the first
-# failure ends the call (no retries).  Output under gpurun_out/<name>.log.
+# failure ends the call (no retries).  Output under $OUT/<name>.log.
 set -o pipefail
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}   # logs and profiler output
+mkdir -p $OUT
 export TMPDIR=/tmp
 run() {  # name, timeout, command...
   local name=$1 t=$2; shift 2
   echo "== $name"
-  timeout -k 10 "$t" "$@" > "gpurun_out/$name.log" 2>&1
+  timeout -k 10 "$t" "$@" > "$OUT/$name.log" 2>&1
   local rc=$?
-  tail -3 "gpurun_out/$name.log" | cut -c1-300
-  if [ $rc -ne 0 ]; then echo "== $name FAILED rc=$rc"; tail -40 "gpurun_out/$name.log" | cut -c1-300; exit $rc; fi
+  tail -3 "$OUT/$name.log" | cut -c1-300
+  if [ $rc -ne 0 ]; then echo "== $name FAILED rc=$rc"; tail -40 "$OUT/$name.log" | cut -c1-300; exit $rc; fi
 }
-B="python -u bench.py --no-pi --no-tz --no-mc --no-cpu-baseline"
+B="python -u bench.py --full --no-pi --no-tz --no-mc --no-cpu-baseline"
 for step in "$@"; do
   case $step in
     tests) run pytest_gpu 600 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
@@ -56,24 +57,24 @@ for step in "$@"; do
     m10b) run m10tests 400 python -u -m pytest tests/test_gpu_main10.py -m gpu -x -v -p no:cacheprovider --timeout 200 --timeout-method thread && \
           run m10bench 300 $B --workload c3_qp22_main10 --steps 10 --parity-seconds 10 && \
           run m10bench_px 300 env FME_MAIN10_SEARCH=px $B --workload c3_qp22_main10 --steps 10 --parity-seconds 0 ;;
-    copytl_rocpd) run copytl_rocpd 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format rocpd -d gpurun_out/copytl_rocpd -o run -- python3 bench.py --no-pi --no-tz --no-mc --no-cpu-baseline --parity-seconds 0 --steps 10 ;;
-    tl) run tl_c3 200 $B --steps 20 --parity-seconds 0 --timeline gpurun_out/timeline_c3.txt && \
-        run tl_c1 200 $B --workload c1 --steps 20 --parity-seconds 0 --timeline gpurun_out/timeline_c1.txt ;;
+    copytl_rocpd) run copytl_rocpd 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format rocpd -d $OUT/copytl_rocpd -o run -- python3 bench.py --full --no-pi --no-tz --no-mc --no-cpu-baseline --parity-seconds 0 --steps 10 ;;
+    tl) run tl_c3 200 $B --steps 20 --parity-seconds 0 --timeline $OUT/timeline_c3.txt && \
+        run tl_c1 200 $B --workload c1 --steps 20 --parity-seconds 0 --timeline $OUT/timeline_c1.txt ;;
     mc10) run mc10tests 300 python -u -m pytest tests/test_gpu_mc.py tests/test_gpu_main10.py -m gpu -x -v -p no:cacheprovider --timeout 200 --timeout-method thread ;;
     logwait) run env_logwait 200 env AMD_LOG_LEVEL=4 AMD_LOG_MASK=294 $B --steps 12 --parity-seconds 0 ;;
     tzc) run tz_counts 200 python -u tools/tz_counts.py ;;
     icache) A="python tools/ab_bench.py . --rounds 2 --reps 2"
-            run ic_a 90 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS --output-format csv -d gpurun_out/ic/a -o run -- $A && \
-            run ic_b 90 rocprofv3 --pmc SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --output-format csv -d gpurun_out/ic/b -o run -- $A && \
-            run ic_c 90 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d gpurun_out/ic/c -o run -- $A && \
-            python3 tools/pmc_summary.py gpurun_out/ic > gpurun_out/icache.txt ;;
-    bench) run bench 400 python -u bench.py --no-pi --no-tz --no-mc ;;
-    benchfull) run benchfull 600 python -u bench.py ;;
+            run ic_a 90 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS --output-format csv -d $OUT/ic/a -o run -- $A && \
+            run ic_b 90 rocprofv3 --pmc SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --output-format csv -d $OUT/ic/b -o run -- $A && \
+            run ic_c 90 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $OUT/ic/c -o run -- $A && \
+            python3 tools/pmc_summary.py $OUT/ic > $OUT/icache.txt ;;
+    bench) run bench 400 python -u bench.py --full --no-pi --no-tz --no-mc ;;
+    benchfull) run benchfull 600 python -u bench.py --full ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    copytl) run copytl 300 env FME_CRASH_TRACE=1 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d gpurun_out/copytl -o run -- python3 bench.py --no-pi --no-tz --no-mc --no-cpu-baseline --parity-seconds 0 --steps 10 ;;
-    copytl_dbg) run copytl_dbg 300 env FME_CRASH_TRACE=1 LD_DEBUG=files rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d gpurun_out/copytl -o run -- python3 bench.py --no-pi --no-tz --no-mc --no-cpu-baseline --parity-seconds 0 --steps 10 ;;
-    copytl_c1) run copytl_c1 300 env FME_CRASH_TRACE=1 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d gpurun_out/copytl_c1 -o run -- python3 bench.py --workload c1 --no-cpu-baseline --no-pi --no-tz --no-mc --parity-seconds 0 --steps 10 ;;
-    prof) run prof 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run -- python3 bench.py --no-cpu-baseline --no-pi --no-tz --no-mc --parity-seconds 0 --no-pcie ;;
+    copytl) run copytl 300 env FME_CRASH_TRACE=1 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/copytl -o run -- python3 bench.py --full --no-pi --no-tz --no-mc --no-cpu-baseline --parity-seconds 0 --steps 10 ;;
+    copytl_dbg) run copytl_dbg 300 env FME_CRASH_TRACE=1 LD_DEBUG=files rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/copytl -o run -- python3 bench.py --full --no-pi --no-tz --no-mc --no-cpu-baseline --parity-seconds 0 --steps 10 ;;
+    copytl_c1) run copytl_c1 300 env FME_CRASH_TRACE=1 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/copytl_c1 -o run -- python3 bench.py --full --workload c1 --no-cpu-baseline --no-pi --no-tz --no-mc --parity-seconds 0 --steps 10 ;;
+    prof) run prof 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python3 bench.py --full --no-cpu-baseline --no-pi --no-tz --no-mc --parity-seconds 0 --no-pcie ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done
