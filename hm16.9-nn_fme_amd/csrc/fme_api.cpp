@@ -269,8 +269,6 @@ struct fme_ctx {
   hipEvent_t ev_done = nullptr; // end of the last batch (fme_refine_status)
   hipEvent_t ev_search = nullptr; // caller's event, recorded before each search launch (fme_set_search_event)
   int search_reserve = 0;         // resident search workgroups left free (fme_set_search_reserve)
-  fme_ctx* single10 = nullptr;    // bit depth 10: the private one-job context of fme_frac_dif_single
-  hipStream_t single10_stream = nullptr;
   bool main10_px = false;         // bit depth 10: the pixel kernel instead of the lane kernel
                                   // (environment FME_MAIN10_SEARCH=px, an A/B switch)
   bool batch_issued = false;
@@ -376,8 +374,6 @@ int fme_destroy(fme_ctx* c) {
   if (!c) return FME_OK;
   (void)hipSetDevice(c->device);
   (void)srv_stop(c);
-  if (c->single10) (void)fme_destroy(c->single10);
-  if (c->single10_stream) (void)hipStreamDestroy(c->single10_stream);
   (void)hipDeviceSynchronize();
   for (int i = 0; i < FME_MAX_PICTURES; i++)
     if (c->pic_owned[i] && c->pics[i].luma) (void)hipFree(const_cast<uint8_t*>(c->pics[i].luma));
@@ -1531,7 +1527,7 @@ static int srv_launch(fme_ctx* c) {
   const uint32_t epoch = ++c->srv_epoch;
   c->srv_nn_gen = c->nn_gen;
   HIP_TRY(launch_server(c->box_dev, c->nn_loaded ? c->d_nn.p : nullptr, c->srv_done, epoch,
-                        kSrvIdleUs * c->srv_khz / 1000, kSrvLifeMs * c->srv_khz, c->srv_stream));
+                        kSrvIdleUs * c->srv_khz / 1000, kSrvLifeMs * c->srv_khz, c->cfg.bit_depth, c->srv_stream));
   c->srv_running = true;
   return FME_OK;
 }
@@ -1617,63 +1613,9 @@ static int srv_call(fme_ctx* c, bool uses_nn) {
 // and the reference window around the integer MV (rows -4..h+3, columns -4..w+3 of the padded
 // picture) go into the server's mailbox; the MV predictor is shifted by 4*mv_int so that every
 // MV-cost argument (xPatternRefinement's (cMvTest << scale) - pred) is unchanged.
-// Bit depth 10: the call runs as a one-job batch (the lane kernel k_search_lane10, bit-exact with
-// the main10 batches) on a private 10-bit context with its own stream, so the caller's pictures,
-// lambdas, keys and NN state are untouched: the window (rows -4..h+3, columns -4..w+3 around
-// mv_int) becomes picture 0 with the PU at (4, 4), the key its key block, the MV predictor is
-// shifted by 4*mv_int as for the server.  Latency: a few launches and copies per call.
-static int frac_dif_single10(fme_ctx* c, int lossless, const int16_t* key, int key_stride, int w, int h,
-                             const int16_t* ref, int ref_stride, int mv_int_x, int mv_int_y, int px, int py,
-                             double motion_lambda, int16_t* half_xy, int16_t* qtr_xy, uint32_t* cost) {
-  if (!c->single10) {
-    fme_config cfg = c->cfg;
-    cfg.nn_mode = 0;
-    cfg.max_jobs = 64;
-    fme_ctx* s = nullptr;
-    const int rc = fme_create(c->device, &cfg, &s);
-    if (rc) return rc;
-    c->single10 = s;
-    HIP_TRY(hipStreamCreateWithFlags(&c->single10_stream, hipStreamNonBlocking));
-  }
-  fme_ctx* s = c->single10;
-  const int pw = w + 8, ph = h + 8;
-  const int maxv = (1 << c->cfg.bit_depth) - 1;
-  std::vector<uint16_t> win((size_t)pw * ph);
-  for (int y = 0; y < ph; y++) {
-    const int16_t* src = ref + (ptrdiff_t)(mv_int_y - 4 + y) * ref_stride + (mv_int_x - 4);
-    for (int x = 0; x < pw; x++) win[(size_t)y * pw + x] = (uint16_t)std::min(maxv, std::max(0, (int)src[x]));
-  }
-  std::vector<int16_t> kb((size_t)w * h);
-  for (int y = 0; y < h; y++) std::memcpy(&kb[(size_t)y * w], key + (ptrdiff_t)y * key_stride, (size_t)w * sizeof(int16_t));
-  int rc = fme_set_picture(s, 0, reinterpret_cast<const uint8_t*>(win.data()), pw, pw, ph, c->single10_stream);
-  if (!rc) rc = fme_set_motion_lambda(s, 0, motion_lambda);
-  if (!rc) rc = fme_set_keys(s, kb.data(), kb.size(), c->single10_stream);
-  if (rc) return rc;
-  fme_job j{};
-  j.x = 4;
-  j.y = 4;
-  j.w = (uint8_t)w;
-  j.h = (uint8_t)h;
-  j.org_id = 0;
-  j.ref_id = 0;
-  j.mvp_x = (int16_t)px;
-  j.mvp_y = (int16_t)py;
-  j.lt_x = j.lt_y = -1;
-  j.rb_x = j.rb_y = 1;
-  j.flags = lossless ? FME_JOB_LOSSLESS : 0;
-  j.key_offset = 0;
-  fme_result r{};
-  rc = fme_refine(s, &j, &r, 1, c->single10_stream);
-  if (rc) return rc;
-  if (r.status & FME_RES_REJECTED) return fail(FME_E_INVALID, "fme_frac_dif_single: job rejected");
-  half_xy[0] = r.half_x;
-  half_xy[1] = r.half_y;
-  qtr_xy[0] = r.qtr_x;
-  qtr_xy[1] = r.qtr_y;
-  *cost = r.frac_cost;
-  return FME_OK;
-}
-
+// Both bit depths go through the same mailbox: the context's depth picks the server instance
+// (k_server<8> / k_server<10>) and the window's sample size (srv_pack_frac, fme_srv_pack.h), so
+// the caller's pictures, lambdas, keys and NN state are untouched at either depth.
 int fme_frac_dif_single(fme_ctx* c, int lossless, const int16_t* key, int key_stride, int w, int h,
                         const int16_t* ref, int ref_stride, int mv_int_x, int mv_int_y, int mvp_x,
                         int mvp_y, double motion_lambda, int16_t* half_xy, int16_t* qtr_xy,
@@ -1684,39 +1626,12 @@ int fme_frac_dif_single(fme_ctx* c, int lossless, const int16_t* key, int key_st
   const int px = mvp_x - 4 * mv_int_x, py = mvp_y - 4 * mv_int_y;
   if (px < -32768 || px > 32767 || py < -32768 || py > 32767) return fail(FME_E_INVALID, "fme_frac_dif_single: predictor out of range");
   HIP_TRY(hipSetDevice(c->device));
-  if (c->cfg.bit_depth > 8)
-    return frac_dif_single10(c, lossless, key, key_stride, w, h, ref, ref_stride, mv_int_x, mv_int_y, px, py,
-                             motion_lambda, half_xy, qtr_xy, cost);
   int rc = srv_open(c);
   if (rc) return rc;
   SrvBox* b = c->box;
-  const uint32_t seq = c->srv_done + 1;   // the call's sequence number (srv_call)
-  const int pw = w + 8, ph = h + 8, win_bytes = pw * ph, bytes = win_bytes + 2 * w * h;
-  // small PUs: window and key ride in the request blocks (kSrvTagged), 12 bytes per block
-  const bool tagged = bytes <= kSrvTagBytes;
-  alignas(16) uint8_t stream[kSrvTagBytes + 12];
-  uint8_t* wdst = tagged ? stream : b->win;
-  int16_t* kdst = tagged ? reinterpret_cast<int16_t*>(stream + win_bytes) : b->key;
-  for (int y = 0; y < h; y++) std::memcpy(kdst + y * w, key + (ptrdiff_t)y * key_stride, (size_t)w * sizeof(int16_t));
-  for (int y = 0; y < ph; y++) {
-    const int16_t* src = ref + (ptrdiff_t)(mv_int_y - 4 + y) * ref_stride + (mv_int_x - 4);
-    uint8_t* dst = wdst + y * pw;
-    for (int x = 0; x < pw; x++) dst[x] = (uint8_t)std::min(255, std::max(0, (int)src[x]));
-  }
-  if (tagged)
-    for (int p = 0; 12 * p < bytes; p++) {
-      std::memcpy(&b->req[2 + p][1], stream + 12 * p, 12);
-      __atomic_store_n(&b->req[2 + p][0], seq, __ATOMIC_RELEASE);
-    }
-  uint32_t mlw[2];
-  std::memcpy(mlw, &motion_lambda, sizeof(mlw));
-  b->req[1][1] = mlw[0];
-  b->req[1][2] = mlw[1];
-  __atomic_store_n(&b->req[1][0], seq, __ATOMIC_RELEASE);
-  b->req[0][1] = (uint32_t)kSrvFrac | ((lossless || !c->cfg.use_hadamard) ? (uint32_t)kSrvSad : 0u) |
-                 (tagged ? (uint32_t)kSrvTagged : 0u) | (c->srv_marks ? (uint32_t)kSrvMarks : 0u) |
-                 ((uint32_t)(w - 1) << 8) | ((uint32_t)(h - 1) << 16);
-  b->req[0][2] = (uint32_t)(uint16_t)px | ((uint32_t)(uint16_t)py << 16);
+  // request blocks, payload, shape and predictor; srv_call publishes the sequence word
+  srv_pack_frac(b, c->srv_done + 1, c->cfg.bit_depth, lossless || !c->cfg.use_hadamard, c->srv_marks, key, key_stride, w,
+                h, ref, ref_stride, mv_int_x, mv_int_y, px, py, motion_lambda);
   rc = srv_call(c, false);
   if (rc) return rc;
   const uint32_t hq = b->res[2];

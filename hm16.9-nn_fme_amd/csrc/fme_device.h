@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/fme.h"
+#include "fme_srv_pack.h"
 
 // 0 (default): k_scatter writes only the permutation and the searches gather jobs[perm[i]];
 // 1: k_scatter also copies each job into class order (sjobs) for contiguous reads.  Same search
@@ -268,37 +269,11 @@ hipError_t launch_search_lane10(const BatchArgs& a, const WorkBufs& w, hipStream
 struct NnIn11 {   // NN_pred() inputs of a single call: array_e slots[8], C, PUHeight, PUWidth
   uint32_t v[11];
 };
-// The single-call server (fme_server.hip): one resident workgroup polls `req_seq` in this block of
-// pinned, device-mapped host memory, serves the call and stores the answer block `res`; `stopped` = the
-// epoch of an instance that exited (idle, lifetime or `stop`).  Request fields share the first
-// lines, the answer has its own, the payload follows.
-enum { kSrvNn = 1, kSrvFrac = 2, kSrvSad = 4, kSrvTagged = 8, kSrvMarks = 16 };
-constexpr int kSrvBlocks = 128;                       // request blocks, all read by every poll
-constexpr int kSrvTagBytes = 12 * (kSrvBlocks - 2);   // FracDIF payload that rides in the blocks
-struct SrvBox {
-  // host -> device, in 16-byte blocks that the polling wave reads all at once (two per lane, one
-  // load each), so a block's fields are those written before its sequence word.  req[0]: seq,
-  // shape = kind (bits 0-1) | kSrvSad (lossless or HADME off) | kSrvTagged | kSrvMarks (record the
-  // phase checkpoints in `marks`) | w - 1 (bits 8-15) |
-  // h - 1 (bits 16-23), the FracDIF predictor - 4 * integer MV (x low 16 bits, y high 16,
-  // quarter-pel), stop (set by the host to end the instance).  The rest carry this call's seq in
-  // word 0 and are taken only when every one the call uses does:
-  //   NN_pred: req[1..4], three inputs each (array_e[8], C, PUHeight, PUWidth);
-  //   FracDIF: req[1] = the motion lambda (TComRdCost::m_motionLambda, a double in words 1-2);
-  //   kSrvTagged: req[2..] = the window then the key, 12 bytes per block, when they fit in
-  //   kSrvTagBytes (the payload arrives with the request: no second round trip); otherwise they are
-  //   in key / win below, read after the request.
-  alignas(64) uint32_t req[kSrvBlocks][4];
-  // device -> host, one 16-byte store: seq, FracDIF cost / NN class, FracDIF half x, y and quarter
-  // x, y as int8 (bytes 0..3), the call's device ticks (request read to answer)
-  alignas(64) uint32_t res[4];
-  uint32_t marks[4];           // FracDIF checkpoints of the call (fme_single_last_device_us)
-  uint32_t stopped;
-  alignas(64) int16_t key[64 * 64];   // w * h (a multiple of 16 bytes for every PU shape)
-  alignas(16) uint8_t win[72 * 72 + 16];   // (w + 8) x (h + 8) window around the integer MV, stride w + 8
-};
+// The single-call server (fme_server.hip): its mailbox SrvBox, the request-block count and the
+// payload mapping live in fme_srv_pack.h (shared with the host's packing code).  bit_depth selects
+// the kernel instance (a context has one depth).
 hipError_t launch_server(SrvBox* box, const float* nn, uint32_t served, uint32_t epoch, uint64_t idle_ticks,
-                         uint64_t life_ticks, hipStream_t s);
+                         uint64_t life_ticks, int bit_depth, hipStream_t s);
 int lane_lanes_per_pu(int cls);                    // lanes of a class's PU group (pow2), 0: none
 int cu_count(int device);                          // compute units (workgroup budget of a launch)
 // Packed NN layout for the tail kernel (nn_pack, fme_kernels.hip): offsets in floats, every

@@ -3,7 +3,7 @@
 // TEncSearch calls xPatternSearchFracDIF (TEncSearch.cpp:5232-5269) and NN_pred (85-204) once per
 // PU, so the drop-in entry points are latency-bound: a kernel launch plus its completion costs
 // more than the work.  Instead one workgroup stays resident while calls keep coming: it polls a
-// request word in pinned, device-mapped host memory (SrvBox, fme_device.h), serves the call with
+// request word in pinned, device-mapped host memory (SrvBox, fme_srv_pack.h), serves the call with
 // all 16 of its waves, writes the answer back to host memory and releases a completion word the
 // host spins on.  It exits after kSrv idle time without a request, after its lifetime, or when
 // the host sets `stop`, and says so in `stopped` (the instance's epoch); the host relaunches it on
@@ -14,8 +14,17 @@
 // wave per (candidate, block), the separable filter's first stage for the three fractional phases
 // computed once into LDS, SATD butterflies across lanes.  Same arithmetic as the batch kernel and
 // the oracle (orc_frac_dif): bit-exact.
+//
+// The FracDIF side is a template on the context's bit depth (k_server<8>, k_server<10>; a context
+// has one depth, so the host picks the instance at launch and no request carries it): 10-bit
+// windows are uint16_t samples in LDS and in the mailbox, the filter stages run at 14 - 10 bits of
+// head room like k_search_lane10, and the summed distortion is shifted by bitDepth - 8 once per
+// candidate.  The mailbox layout, the request-block count and the payload mapping come from
+// fme_srv_pack.h, which the host packs with.
 #include "fme_device.h"
 #include "fme_xlane.h"
+
+#include <type_traits>
 
 namespace fme {
 namespace {
@@ -72,11 +81,16 @@ __device__ __forceinline__ uint32_t eg_bits_d(int v) {
   return 2u * (31u - (uint32_t)__clz((int)t)) + 1u;
 }
 
+// BD: the context's bit depth (8 or 10); window samples are uint8_t at 8 bits, uint16_t at 10
+// (0..1023), everything else has one layout.  The 16 samples after the window take the end of the
+// untagged window's last 16-byte load.
+template <int BD>
 struct SrvLds {
+  typedef typename std::conditional<(BD > 8), uint16_t, uint8_t>::type Sample;
   float nn[kNnPkFloats];
   alignas(16) int16_t key[64 * 64];
   int16_t hp[3][72 * 65];       // first filter stage, fractional phase 1..3, columns -1 .. w-1
-  alignas(16) uint8_t win[72 * 72 + 16];
+  alignas(16) Sample win[72 * 72 + 16];
   uint32_t cost[2][16];           // per candidate: half stage, quarter stage
   int32_t ctl[10];              // stop, seq, kind, w, h, mvp_x, mvp_y, sad, tagged, marks
   uint32_t nn_in[12];
@@ -89,8 +103,11 @@ struct SrvLds {
 
 // Distortion of block group b of the PU at quarter-pel offset (ox, oy) from the integer MV (wave-
 // uniform), lanes = the group's pixels: 8x8 SATD, four 4x4 SATDs or SAD, summed over the wave.
-template <bool SAD, bool B8>
-__device__ __forceinline__ uint32_t item_dist(const SrvLds& L, int w, int nb4, int b, int ox, int oy, int lane) {
+// Bit depth BD: head room 14 - BD (TComInterpolationFilter's IF_INTERNAL_PREC - bitDepth), the
+// prediction clipped to 0 .. 2^BD - 1; the key may be a bi-pred key (-1023 .. 2046 at 10 bits), so
+// |d| <= 3069, an 8x8 Hadamard coefficient < 2^18 and a 64x64 PU's sum < 2^30: int32 throughout.
+template <int BD, bool SAD, bool B8>
+__device__ __forceinline__ uint32_t item_dist(const SrvLds<BD>& L, int w, int nb4, int b, int ox, int oy, int lane) {
   const int bw8 = w >> 3, bw4 = w >> 2;
   int c, r;
   bool valid = true;
@@ -112,10 +129,11 @@ __device__ __forceinline__ uint32_t item_dist(const SrvLds& L, int w, int nb4, i
   const int x = c + ix, wy0 = r + iy + 4;
   // first-stage samples at window rows wy0 - 3 .. wy0 + 4: the 14-bit values m_filteredBlockTmp
   // holds (filterHor with isLast false; filterCopy's isFirst branch for fraction 0)
+  constexpr int kHead = 14 - BD;
   int hs[8];
   if (fx == 0) {
 #pragma unroll
-    for (int t = 0; t < 8; t++) hs[t] = ((int)L.win[(wy0 + t - 3) * (w + 8) + x + 4] << 6) - 8192;
+    for (int t = 0; t < 8; t++) hs[t] = ((int)L.win[(wy0 + t - 3) * (w + 8) + x + 4] << kHead) - 8192;
   } else {
     const int16_t* hp = L.hp[fx - 1] + x + 1;
 #pragma unroll
@@ -123,14 +141,14 @@ __device__ __forceinline__ uint32_t item_dist(const SrvLds& L, int w, int nb4, i
   }
   int v;
   if (fy == 0) {
-    v = (hs[3] + 8192 + 32) >> 6;                        // filterCopy, !isFirst isLast
+    v = (hs[3] + 8192 + (1 << (kHead - 1))) >> kHead;    // filterCopy, !isFirst isLast
   } else {
     int s = 0;
 #pragma unroll
     for (int t = 0; t < 8; t++) s += luma_tap(fy, t) * hs[t];
-    v = (s + 2048 + (8192 << 6)) >> 12;                  // filter<8, true, false, true>
+    v = (s + (1 << (kHead + 5)) + (8192 << 6)) >> (kHead + 6);   // filter<8, true, false, true>
   }
-  v = min(255, max(0, v));
+  v = min((1 << BD) - 1, max(0, v));
   int d = valid ? (int)L.key[r * w + c] - v : 0;
   uint32_t add;
   if constexpr (SAD) {
@@ -156,13 +174,13 @@ __device__ __forceinline__ uint32_t item_dist(const SrvLds& L, int w, int nb4, i
 // (ox, oy) of candidate k = base + 2 * ref (half) or base + ref (quarter), quarter-pel offsets from
 // the integer MV.  Work item (candidate, block) per wave; lanes are the block's pixels.
 // SAD: lossless or HADME off; B8: xGetHADs' 8x8 transform (both dimensions multiples of 8).
-template <bool SAD, bool B8>
+template <int BD, bool SAD, bool B8>
 #ifdef FME_SRV_NOINL
 __device__ __noinline__
 #else
 __device__
 #endif
-void stage_dist(SrvLds& L, int w, int h, bool half, int bx0, int by0) {
+void stage_dist(SrvLds<BD>& L, int w, int h, bool half, int bx0, int by0) {
   const int lane = (int)threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   constexpr bool b8 = B8;
   const int nb4 = (w >> 2) * (h >> 2);
@@ -187,13 +205,16 @@ void stage_dist(SrvLds& L, int w, int h, bool half, int bx0, int by0) {
     }
     const int ox = bx0 + (half ? 2 * ref_of(kRefHx, k) : ref_of(kRefQx, k));
     const int oy = by0 + (half ? 2 * ref_of(kRefHy, k) : ref_of(kRefQy, k));
-    acc += item_dist<SAD, B8>(L, w, nb4, b, ox, oy, lane);
+    acc += item_dist<BD, SAD, B8>(L, w, nb4, b, ox, oy, lane);
   }
   if (i0 < i1 && lane == 0) atomicAdd(&L.cost[half ? 0 : 1][kcur], acc);
 }
 
 // Wave 0: distortion + MV cost per candidate (lane k), the first strict minimum in candidate order.
-__device__ void stage_pick(const SrvLds& L, bool half, int hx, int hy, int& best_k, uint32_t& best) {
+// Bit depth BD: xGetHADs / xGetSAD return uiSum >> (BD - 8) over the whole PU (TComRdCost.cpp
+// DISTORTION_PRECISION_ADJUSTMENT), so the candidate's summed distortion is shifted here, once.
+template <int BD>
+__device__ void stage_pick(const SrvLds<BD>& L, bool half, int hx, int hy, int& best_k, uint32_t& best) {
   const int lane = (int)threadIdx.x & 63;
   const int px = L.ctl[5], py = L.ctl[6];
   uint32_t tot = 0xFFFFFFFFu;
@@ -203,7 +224,7 @@ __device__ void stage_pick(const SrvLds& L, bool half, int hx, int hy, int& best
     const int mx = half ? 2 * ref_of(kRefHx, lane) : 2 * hx + ref_of(kRefQx, lane);
     const int my = half ? 2 * ref_of(kRefHy, lane) : 2 * hy + ref_of(kRefQy, lane);
     const uint32_t bits = eg_bits_d(mx - px) + eg_bits_d(my - py);
-    tot = L.cost[half ? 0 : 1][lane] + (uint32_t)((L.ml * (double)bits) / 65536.0);
+    tot = (L.cost[half ? 0 : 1][lane] >> (BD - 8)) + (uint32_t)((L.ml * (double)bits) / 65536.0);
   }
   int k = lane < 9 ? lane : 64;
   auto step = [&](uint32_t ot, int ok) {
@@ -220,7 +241,11 @@ __device__ void stage_pick(const SrvLds& L, bool half, int hx, int hy, int& best
   best = tot;
 }
 
-__device__ void serve_frac(SrvLds& L, SrvBox* box, uint64_t t_req) {
+template <int BD>
+__device__ void serve_frac(SrvLds<BD>& L, SrvBox* box, uint64_t t_req) {
+  typedef typename SrvLds<BD>::Sample Sample;
+  // filterHor with isLast false: (sum - (8192 << shift)) >> shift, shift = BD - 8
+  constexpr int kS1 = BD - 8;
   const int tid = (int)threadIdx.x;
   const bool marks = L.ctl[9] != 0;   // checkpoints only when asked for (each is a wall-clock read)
   auto mark = [&](int m) {
@@ -238,11 +263,11 @@ __device__ void serve_frac(SrvLds& L, SrvBox* box, uint64_t t_req) {
       const int f = __builtin_amdgcn_readfirstlane(i) / span, j = i - f * span;
       if (j < plane) {
         const int wy = j / cols, xr = j - wy * cols;
-        const uint8_t* row = L.win + wy * pw + xr;   // taps at window columns x + 4 - 3 ...
+        const Sample* row = L.win + wy * pw + xr;   // taps at window columns x + 4 - 3 ...
         int s = 0;
 #pragma unroll
         for (int t = 0; t < 8; t++) s += luma_tap(f + 1, t) * (int)row[t];
-        L.hp[f][j] = (int16_t)(s - 8192);
+        L.hp[f][j] = (int16_t)((s - (8192 << kS1)) >> kS1);
       }
     }
   } else {   // thread (xr, rr): column xr - 1 of rows rr, rr + 8, ... of the three phases' planes
@@ -250,11 +275,11 @@ __device__ void serve_frac(SrvLds& L, SrvBox* box, uint64_t t_req) {
     if (xr < cols)
       for (int R = tid >> 7; R < 3 * ph; R += kSrvThreads >> 7) {
         const int f = R >= 2 * ph ? 2 : (R >= ph ? 1 : 0), wy = R - f * ph;
-        const uint8_t* row = L.win + wy * pw + xr;
+        const Sample* row = L.win + wy * pw + xr;
         int s = 0;
 #pragma unroll
         for (int t = 0; t < 8; t++) s += luma_tap(f + 1, t) * (int)row[t];
-        L.hp[f][wy * cols + xr] = (int16_t)(s - 8192);
+        L.hp[f][wy * cols + xr] = (int16_t)((s - (8192 << kS1)) >> kS1);
       }
   }
   __syncthreads();
@@ -262,11 +287,11 @@ __device__ void serve_frac(SrvLds& L, SrvBox* box, uint64_t t_req) {
   // one stage's distortions, specialised on the transform
   auto dist = [&](bool half, int bx0, int by0) {
     if (sad)
-      stage_dist<true, false>(L, w, h, half, bx0, by0);
+      stage_dist<BD, true, false>(L, w, h, half, bx0, by0);
     else if ((w & 7) == 0 && (h & 7) == 0)
-      stage_dist<false, true>(L, w, h, half, bx0, by0);
+      stage_dist<BD, false, true>(L, w, h, half, bx0, by0);
     else
-      stage_dist<false, false>(L, w, h, half, bx0, by0);
+      stage_dist<BD, false, false>(L, w, h, half, bx0, by0);
   };
   dist(true, 0, 0);
   __syncthreads();
@@ -274,7 +299,7 @@ __device__ void serve_frac(SrvLds& L, SrvBox* box, uint64_t t_req) {
   if (tid < 64) {
     int k;
     uint32_t best;
-    stage_pick(L, true, 0, 0, k, best);
+    stage_pick<BD>(L, true, 0, 0, k, best);
     if (tid == 0) {
       L.sel[0] = ref_of(kRefHx, k);
       L.sel[1] = ref_of(kRefHy, k);
@@ -288,7 +313,7 @@ __device__ void serve_frac(SrvLds& L, SrvBox* box, uint64_t t_req) {
   if (tid < 64) {
     int k;
     uint32_t best;
-    stage_pick(L, false, hx, hy, k, best);
+    stage_pick<BD>(L, false, hx, hy, k, best);
     if (tid == 0) {
       L.ans[0] = best;
       L.ans[1] = (uint32_t)(uint8_t)hx | ((uint32_t)(uint8_t)hy << 8) | ((uint32_t)(uint8_t)ref_of(kRefQx, k) << 16) |
@@ -309,7 +334,10 @@ __device__ __forceinline__ float lane_f(float v, int l) {
 // element (row r, k) of a packed [row pairs][K][2] matrix
 __device__ __forceinline__ int pk_at(int base, int K, int r, int k) { return base + ((r >> 1) * K + k) * 2 + (r & 1); }
 __device__ __forceinline__ float relu1(float s) { return s < 0.0f ? 0.0f : s; }
-__device__ void serve_nn(SrvLds& L, SrvBox* box) {
+// Depth-independent: one definition for both instances; the parameter only names the instance's LDS
+// block (and gives each kernel its own copy to inline, as the single kernel had).
+template <int BD>
+__device__ void serve_nn(SrvLds<BD>& L, SrvBox* box) {
   const int r = (int)threadIdx.x;
   if (r >= 64) return;
   const float* Q = L.nn;
@@ -377,9 +405,11 @@ __device__ void serve_nn(SrvLds& L, SrvBox* box) {
   }
 }
 
+template <int BD>
 __global__ __launch_bounds__(kSrvThreads) void k_server(SrvBox* box, const float* nn, uint32_t served, uint32_t epoch,
                                                         uint64_t idle_ticks, uint64_t life_ticks) {
-  __shared__ SrvLds L;
+  __shared__ SrvLds<BD> L;
+  constexpr int kBps = srv_bps(BD);   // bytes per window sample
   const int tid = (int)threadIdx.x;
   if (nn)
     for (int i = tid; i < kNnPkFloats; i += kSrvThreads) L.nn[i] = nn[i];
@@ -399,7 +429,7 @@ __global__ __launch_bounds__(kSrvThreads) void k_server(SrvBox* box, const float
           need = 4;   // blocks 1..need must all be this call's
           if ((shape & 3u) == kSrvFrac) {
             const int w = (int)((shape >> 8) & 0xFFu) + 1, h = (int)((shape >> 16) & 0xFFu) + 1;
-            need = (shape & kSrvTagged) ? 1 + ((w + 8) * (h + 8) + 2 * w * h + 11) / 12 : 1;
+            need = srv_frac_need((shape & kSrvTagged) != 0, w, h, kBps);
           }
           if (__ballot((lane >= 1 && lane <= need && hd.x != seq) || (lane + 64 <= need && hb.x != seq)) == 0) break;
           // a block still carries an older call's sequence word: poll again, but the stop word and the
@@ -437,19 +467,10 @@ __global__ __launch_bounds__(kSrvThreads) void k_server(SrvBox* box, const float
         if (lane == 1) L.ml = __builtin_bit_cast(double, (uint64_t)hd.y | ((uint64_t)hd.z << 32));
         if (shape & kSrvTagged) {   // the payload words of blocks 2..need: window, then key
           const int w = (int)((shape >> 8) & 0xFFu) + 1, h = (int)((shape >> 16) & 0xFFu) + 1;
-          const int winw = (w + 8) * (h + 8) / 4, totw = winw + w * h / 2;
+          const int winw = srv_win_words(w, h, kBps), totw = srv_payload_words(w, h, kBps);
           uint32_t* wd = reinterpret_cast<uint32_t*>(L.win);
           uint32_t* kd = reinterpret_cast<uint32_t*>(L.key);
-          auto put = [&](int blk, const u32x4& v) {
-            if (blk < 2 || blk > need) return;
-            const uint32_t x[3] = {v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-              const int q = 3 * (blk - 2) + k;
-              if (q < winw) wd[q] = x[k];
-              else if (q < totw) kd[q - winw] = x[k];
-            }
-          };
+          auto put = [&](int blk, const u32x4& v) { srv_put_block(wd, kd, blk, need, winw, totw, v.y, v.z, v.w); };
           put(lane, hd);
           put(lane + 64, hb);
         }
@@ -465,27 +486,27 @@ __global__ __launch_bounds__(kSrvThreads) void k_server(SrvBox* box, const float
         // one request per block (the window's last block may read into the padding after it)
         const uint32_t* wsrc = reinterpret_cast<const uint32_t*>(box->win);
         u32x4* wdst = reinterpret_cast<u32x4*>(L.win);
-        for (int i = tid; i < ((w + 8) * (h + 8) + 15) >> 4; i += kSrvThreads) wdst[i] = load_block(wsrc + 4 * i);
+        for (int i = tid; i < srv_win_loads(w, h, kBps); i += kSrvThreads) wdst[i] = load_block(wsrc + 4 * i);
         const uint32_t* ksrc = reinterpret_cast<const uint32_t*>(box->key);
         u32x4* kdst = reinterpret_cast<u32x4*>(L.key);
-        for (int i = tid; i < (w * h) >> 3; i += kSrvThreads) kdst[i] = load_block(ksrc + 4 * i);
+        for (int i = tid; i < srv_key_loads(w, h); i += kSrvThreads) kdst[i] = load_block(ksrc + 4 * i);
         __syncthreads();
       }
       if (L.ctl[9] && tid == 0) L.mark[0] = (uint32_t)(wall_clock64() - t_req);
     }
     const uint32_t seq = (uint32_t)L.ctl[1];
     if (L.ctl[2] == kSrvFrac) {
-      serve_frac(L, box, t_req);
+      serve_frac<BD>(L, box, t_req);
     } else if (L.ctl[9]) {   // marks: shader-clock cycles and wall ticks of the net itself
       const uint64_t c0 = clock64(), w0 = wall_clock64();
-      serve_nn(L, box);
+      serve_nn<BD>(L, box);
       if (tid == 0) {
         L.mark[0] = (uint32_t)(clock64() - c0);
         L.mark[1] = (uint32_t)(wall_clock64() - w0);
         L.mark[2] = L.mark[3] = 0;
       }
     } else {
-      serve_nn(L, box);
+      serve_nn<BD>(L, box);
     }
     __syncthreads();
     if (tid == 0) {   // the answer and its sequence word in one 16-byte store, past the caches
@@ -505,8 +526,11 @@ __global__ __launch_bounds__(kSrvThreads) void k_server(SrvBox* box, const float
 }  // namespace
 
 hipError_t launch_server(SrvBox* box, const float* nn, uint32_t served, uint32_t epoch, uint64_t idle_ticks,
-                         uint64_t life_ticks, hipStream_t s) {
-  hipLaunchKernelGGL(k_server, dim3(1), dim3(kSrvThreads), 0, s, box, nn, served, epoch, idle_ticks, life_ticks);
+                         uint64_t life_ticks, int bit_depth, hipStream_t s) {
+  if (bit_depth > 8)
+    hipLaunchKernelGGL(k_server<10>, dim3(1), dim3(kSrvThreads), 0, s, box, nn, served, epoch, idle_ticks, life_ticks);
+  else
+    hipLaunchKernelGGL(k_server<8>, dim3(1), dim3(kSrvThreads), 0, s, box, nn, served, epoch, idle_ticks, life_ticks);
   return hipGetLastError();
 }
 

@@ -30,6 +30,23 @@ std::string library_dir() {
 
 int weight_set(int qp) { return (qp == 27 || qp == 32 || qp == 37) ? qp : 22; }  // TEncSearch.cpp:472/625/775/925
 
+// A Pel plane into width-packed samples of type T, every sample within 0 .. maxv.
+template <typename T>
+void stage_plane(const Pel* src, int stride, int w, int h, int maxv, T* dst, const char* what) {
+  for (int r = 0; r < h; r++)
+    for (int c = 0; c < w; c++) {
+      const int v = src[(ptrdiff_t)r * stride + c];
+      if (v < 0 || v > maxv) throw Error(FME_E_UNSUPPORTED, std::string(what) + ": sample outside the bit depth's range");
+      dst[(size_t)r * w + c] = (T)v;
+    }
+}
+
+// The sample width of a plane argument against the search's depth.
+void need_depth(const FracSearch& s, bool wide, const char* what) {
+  if ((s.bitDepth() > 8) != wide)
+    throw Error(FME_E_INVALID, std::string(what) + (wide ? ": 16-bit planes on an 8-bit search" : ": 8-bit planes on a 10-bit search"));
+}
+
 }  // namespace
 
 std::vector<float> loadWeights(const std::string& dir_in, int qp) {
@@ -55,7 +72,7 @@ std::vector<float> loadWeights(const std::string& dir_in, int qp) {
 
 FracSearch::FracSearch(const SearchConfig& cfg) : cfg_(cfg) {
   fme_config c{};
-  c.bit_depth = 8;
+  c.bit_depth = cfg.bitDepth;
   c.use_hadamard = cfg.useHadamardME ? 1 : 0;
   c.nn_mode = cfg.nnMode;
   c.qp = cfg.qp;
@@ -106,22 +123,31 @@ int FracSearch::NN_pred(const uint32_t arrayE[8], uint32_t C, int puHeight, int 
 
 void FracSearch::setPicture(int id, const Pel* plane, int stride, int width, int height) {
   std::lock_guard<std::mutex> lk(mu_);
-  stage_.resize((size_t)width * height);
-  for (int y = 0; y < height; y++) {
-    const Pel* s = plane + (ptrdiff_t)y * stride;
-    uint8_t* d = stage_.data() + (size_t)y * width;
-    for (int x = 0; x < width; x++) {
-      const int v = s[x];
-      if (v < 0 || v > 255) throw Error(FME_E_UNSUPPORTED, "setPicture: sample outside 8-bit range");
-      d[x] = (uint8_t)v;
-    }
+  const int maxv = (1 << cfg_.bitDepth) - 1;
+  if (cfg_.bitDepth > 8) {
+    stage16_.resize((size_t)width * height);
+    stage_plane(plane, stride, width, height, maxv, stage16_.data(), "setPicture");
+    // at bit depth 10 fme_set_picture takes uint16_t samples and the stride in samples
+    check(fme_set_picture(ctx_, id, reinterpret_cast<const uint8_t*>(stage16_.data()), width, width, height, nullptr),
+          "fme_set_picture");
+    return;
   }
+  stage_.resize((size_t)width * height);
+  stage_plane(plane, stride, width, height, maxv, stage_.data(), "setPicture");
   check(fme_set_picture(ctx_, id, stage_.data(), width, width, height, nullptr), "fme_set_picture");
 }
 
 void FracSearch::setPicture8(int id, const uint8_t* plane, int stride, int width, int height) {
+  need_depth(*this, false, "setPicture8");
   std::lock_guard<std::mutex> lk(mu_);
   check(fme_set_picture(ctx_, id, plane, stride, width, height, nullptr), "fme_set_picture");
+}
+
+void FracSearch::setPicture16(int id, const uint16_t* plane, int stride, int width, int height) {
+  need_depth(*this, true, "setPicture16");
+  std::lock_guard<std::mutex> lk(mu_);
+  check(fme_set_picture(ctx_, id, reinterpret_cast<const uint8_t*>(plane), stride, width, height, nullptr),
+        "fme_set_picture");
 }
 
 void FracSearch::setLambdaSlot(int lambdaId, double lambda) {
@@ -134,29 +160,46 @@ void FracSearch::setLambdaSlot(int lambdaId, double lambda) {
 void MotionCompensator::setPictureYuv(int id, const Pel* y, int ys, const Pel* cb, const Pel* cr, int cs, int width,
                                       int height) {
   const int cw = width / 2, ch = height / 2;
-  stage_.resize((size_t)width * height + 2 * (size_t)cw * ch);
-  auto to8 = [&](const Pel* src, int stride, int w, int h, uint8_t* dst) {
-    for (int r = 0; r < h; r++)
-      for (int c = 0; c < w; c++) {
-        const int v = src[(ptrdiff_t)r * stride + c];
-        if (v < 0 || v > 255) throw Error(FME_E_UNSUPPORTED, "setPictureYuv: sample outside 8-bit range");
-        dst[(size_t)r * w + c] = (uint8_t)v;
-      }
-  };
+  const size_t n = (size_t)width * height + 2 * (size_t)cw * ch;
+  const int maxv = (1 << search_.bitDepth()) - 1;
+  if (search_.bitDepth() > 8) {
+    stage16_.resize(n);
+    uint16_t* dy = stage16_.data();
+    uint16_t* dcb = dy + (size_t)width * height;
+    uint16_t* dcr = dcb + (size_t)cw * ch;
+    stage_plane(y, ys, width, height, maxv, dy, "setPictureYuv");
+    stage_plane(cb, cs, cw, ch, maxv, dcb, "setPictureYuv");
+    stage_plane(cr, cs, cw, ch, maxv, dcr, "setPictureYuv");
+    setPictureYuv16(id, dy, width, dcb, dcr, cw, width, height);
+    return;
+  }
+  stage_.resize(n);
   uint8_t* dy = stage_.data();
   uint8_t* dcb = dy + (size_t)width * height;
   uint8_t* dcr = dcb + (size_t)cw * ch;
-  to8(y, ys, width, height, dy);
-  to8(cb, cs, cw, ch, dcb);
-  to8(cr, cs, cw, ch, dcr);
+  stage_plane(y, ys, width, height, maxv, dy, "setPictureYuv");
+  stage_plane(cb, cs, cw, ch, maxv, dcb, "setPictureYuv");
+  stage_plane(cr, cs, cw, ch, maxv, dcr, "setPictureYuv");
   setPictureYuv8(id, dy, width, dcb, dcr, cw, width, height);
 }
 
 void MotionCompensator::setPictureYuv8(int id, const uint8_t* y, int ys, const uint8_t* cb, const uint8_t* cr, int cs,
                                        int width, int height) {
+  need_depth(search_, false, "setPictureYuv8");
   std::lock_guard<std::mutex> lk(search_.mutex());
   check(fme_set_picture(search_.ctx(), id, y, ys, width, height, nullptr), "fme_set_picture");
   check(fme_set_picture_chroma(search_.ctx(), id, cb, cr, cs, nullptr), "fme_set_picture_chroma");
+}
+
+void MotionCompensator::setPictureYuv16(int id, const uint16_t* y, int ys, const uint16_t* cb, const uint16_t* cr, int cs,
+                                        int width, int height) {
+  need_depth(search_, true, "setPictureYuv16");
+  std::lock_guard<std::mutex> lk(search_.mutex());
+  // uint16_t samples, strides in samples (include/fme.h, pictures at bit depth 10)
+  check(fme_set_picture(search_.ctx(), id, reinterpret_cast<const uint8_t*>(y), ys, width, height, nullptr), "fme_set_picture");
+  check(fme_set_picture_chroma(search_.ctx(), id, reinterpret_cast<const uint8_t*>(cb), reinterpret_cast<const uint8_t*>(cr),
+                               cs, nullptr),
+        "fme_set_picture_chroma");
 }
 
 void MotionCompensator::setWp(int list, int id, const int weight[3], const int offset[3], const int log2Denom[3]) {
@@ -191,7 +234,18 @@ void MotionCompensator::add(int x, int y, int w, int h, int cuX, int cuY, int re
   jobs_.push_back(j);
 }
 
+void MotionCompensator::run16(uint16_t* y, int ys, uint16_t* cb, uint16_t* cr, int cs, int width, int height) {
+  need_depth(search_, true, "MotionCompensator::run16");
+  std::lock_guard<std::mutex> lk(search_.mutex());
+  // at bit depth 10 the planes hold uint16_t samples and the strides count samples
+  check(fme_motion_compensate(search_.ctx(), jobs_.data(), (int)jobs_.size(), reinterpret_cast<uint8_t*>(y), ys,
+                              reinterpret_cast<uint8_t*>(cb), reinterpret_cast<uint8_t*>(cr), cs, width, height, nullptr),
+        "fme_motion_compensate");
+  jobs_.clear();
+}
+
 void MotionCompensator::run(uint8_t* y, int ys, uint8_t* cb, uint8_t* cr, int cs, int width, int height) {
+  need_depth(search_, false, "MotionCompensator::run");
   std::lock_guard<std::mutex> lk(search_.mutex());
   check(fme_motion_compensate(search_.ctx(), jobs_.data(), (int)jobs_.size(), y, ys, cb, cr, cs, width, height,
                               nullptr),

@@ -650,9 +650,10 @@ int fme_pred_inter_phases(fme_ctx* ctx, double* ms, int count);
  *   key/key_stride/w/h = pcPatternKey ROI, ref/ref_stride = piRefY/iRefStride
  *   (host pointer at the PU origin of a padded picture: reads span rows -4..h+3 and
  *   columns -4..w+3 around mv_int), mvp/motion_lambda = the TComRdCost state.
- * Synchronous; latency-bound by construction (one launch per call).  At bit depth 10 the
- * call runs as a one-job batch (k_search_lane10) on a private 10-bit context created at the
- * first such call, key and window in int16 / uint16 samples (a few launches and copies).      */
+ * Synchronous; latency-bound by construction.  Both bit depths are served by the resident
+ * single-call server (one instance per context, of the context's depth): at bit depth 10 the
+ * window travels as uint16 samples clamped to 0..1023, and fme_single_last_device_us reports
+ * the call like an 8-bit one.                                                                */
 int fme_frac_dif_single(fme_ctx* ctx, int lossless, const int16_t* key, int key_stride, int w,
                         int h, const int16_t* ref, int ref_stride, int mv_int_x, int mv_int_y,
                         int mvp_x, int mvp_y, double motion_lambda, int16_t* half_xy,

@@ -13,7 +13,12 @@
 //     worker thread that runs it on the GPU while the caller fills the next row, and returns
 //     the results in queue order (the NN's carried state follows queue order across rows).
 //
-// Pel planes are HM's int16 samples; pictures are converted to the library's 8-bit planes.
+// Pel planes are HM's int16 samples; pictures are converted to the library's planes at the
+// search's bit depth (SearchConfig::bitDepth): uint8_t samples at 8 bits, uint16_t at 10 (the
+// main10 configurations, InternalBitDepth 10).  The depth belongs to the context: beyond the picture
+// setters and MotionCompensator's output planes nothing in this header depends on it
+// (xPatternSearchFracDIF, NN_pred, CtuRowBatcher, InterSearchP / InterSearchB and setWp pass
+// through to a context that already has its depth).
 // Errors throw fme_hm::Error carrying fme_last_error().
 #pragma once
 
@@ -31,7 +36,8 @@
 
 namespace fme_hm {
 
-typedef int16_t Pel;          // TypeDef.h:228 (8-bit build: values 0..255; bi-pred keys wider)
+typedef int16_t Pel;          // TypeDef.h:228 (samples 0 .. 2^bitDepth - 1: 0..255 or 0..1023; bi-pred
+                              // keys 2*org - pred are wider: -255..510 or -1023..2046)
 typedef uint32_t Distortion;  // TypeDef.h:239
 
 struct Mv {                   // TComMv (TComMv.h:51-165): hor/ver in the caller's units
@@ -58,6 +64,7 @@ struct SearchConfig {
   int maxJobs = 1 << 16;      // device work buffers sized for this many jobs per row
   std::string weightsDir;     // holds nn2_qp{22,27,32,37}.bin (empty: $FME_WEIGHTS_DIR or the
                               // package's weights/ directory next to libfme_amd.so)
+  int bitDepth = 8;           // InternalBitDepth: 8 or 10 (anything else: Error, FME_E_UNSUPPORTED)
 };
 
 // Reads weights/nn2_qp<set>.bin (2060 float64 -> float32, the set TEncSearch::init picks).
@@ -88,11 +95,16 @@ class FracSearch {
               int& mvxQrter, int& mvyHalf, int& mvyQrter);
 
   // Pictures for the batch path: an HM luma plane (Pel, may point into a padded buffer at
-  // the picture origin) becomes device picture `id` (0..FME_MAX_PICTURES-1).
+  // the picture origin) becomes device picture `id` (0..FME_MAX_PICTURES-1).  A sample outside
+  // 0 .. 2^bitDepth - 1 throws FME_E_UNSUPPORTED.  setPicture8 takes 8-bit samples and belongs to
+  // an 8-bit search, setPicture16 16-bit samples and a 10-bit search (strides in samples); the
+  // other pairing throws FME_E_INVALID (the library would misread the plane).
   void setPicture(int id, const Pel* plane, int stride, int width, int height);
   void setPicture8(int id, const uint8_t* plane, int stride, int width, int height);
+  void setPicture16(int id, const uint16_t* plane, int stride, int width, int height);
   void setLambdaSlot(int lambdaId, double lambda);
 
+  int bitDepth() const { return cfg_.bitDepth; }
   fme_ctx* ctx() const { return ctx_; }
   std::mutex& mutex() { return mu_; }   // serialises context use with a running batcher
 
@@ -102,6 +114,7 @@ class FracSearch {
   double mlambda_ = 0.0;
   Mv mvp_;
   std::vector<uint8_t> stage_;
+  std::vector<uint16_t> stage16_;
   std::mutex mu_;
 };
 
@@ -117,6 +130,10 @@ class MotionCompensator {
                      int height);
   void setPictureYuv8(int id, const uint8_t* y, int yStride, const uint8_t* cb, const uint8_t* cr, int cStride,
                       int width, int height);
+  // 16-bit planes of a 10-bit search (strides in samples); setPictureYuv8 belongs to an 8-bit
+  // search, setPictureYuv16 to a 10-bit one (FME_E_INVALID otherwise)
+  void setPictureYuv16(int id, const uint16_t* y, int yStride, const uint16_t* cb, const uint16_t* cr, int cStride,
+                       int width, int height);
   // Explicit weighted prediction of reference `id` in list `list` (the slice header's
   // WPScalingParam iWeight / iOffset / uiLog2WeightDenom for Y, Cb, Cr; fme_set_wp).
   void setWp(int list, int id, const int weight[3], const int offset[3], const int log2Denom[3]);
@@ -125,13 +142,17 @@ class MotionCompensator {
   void add(int x, int y, int w, int h, int cuX, int cuY, int refIdL0, const Mv& mvL0, int refIdL1, const Mv& mvL1,
            bool weighted = false);
   int pending() const { return (int)jobs_.size(); }
-  // Predict every queued PU into the 8-bit planes (width x height luma) and clear the queue.
+  // Predict every queued PU into the planes (width x height luma) and clear the queue: run into
+  // 8-bit planes on an 8-bit search, run16 into 16-bit planes (samples 0..1023, strides in samples)
+  // on a 10-bit one; the other pairing throws FME_E_INVALID and leaves the queue as it is.
   void run(uint8_t* y, int yStride, uint8_t* cb, uint8_t* cr, int cStride, int width, int height);
+  void run16(uint16_t* y, int yStride, uint16_t* cb, uint16_t* cr, int cStride, int width, int height);
 
  private:
   FracSearch& search_;
   std::vector<fme_mc_job> jobs_;
   std::vector<uint8_t> stage_;
+  std::vector<uint16_t> stage16_;
 };
 
 // TEncSearch::predInterSearch's uni-directional PU / reference loop for P slices
@@ -154,8 +175,8 @@ class InterSearchP {
   std::vector<fme_pu_req> reqs_;
 };
 
-// TEncSearch::predInterSearch for B slices (TEncSearch.cpp:3746-4105; FEN 1/2, MvdL1ZeroFlag
-// false): uni-pred over both lists, the one-iteration bi-pred search on the removeHighFreq key and
+// TEncSearch::predInterSearch for B slices (TEncSearch.cpp:3746-4105; FastInterSearchMode 0-3,
+// MvdL1ZeroFlag false or true): uni-pred over both lists, the one-iteration bi-pred search on the removeHighFreq key and
 // the uni / bi decision, one fme_pu_res_b per fme_pu_req_b.  A CU's second PU must be queued right
 // after its first (uiLastMode).  Same queue discipline as InterSearchP.
 class InterSearchB {

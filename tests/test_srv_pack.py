@@ -1,0 +1,48 @@
+"""The single-call server's mailbox layout (csrc/fme_srv_pack.h), host packing against the kernel's
+block count and payload mapping, on a CPU: tests/cpp/test_srv_pack.cpp built as a stand-alone
+program with AddressSanitizer + UndefinedBehaviorSanitizer (no Python in the sanitized process)
+and run for every PU shape at bit depths 8 and 10."""
+import os
+import shutil
+import subprocess
+
+from conftest import ROOT
+
+SRC = os.path.join(ROOT, "tests", "cpp", "test_srv_pack.cpp")
+INC = os.path.join(ROOT, "hm16.9-nn_fme_amd", "csrc")
+
+
+def _compiler():
+    for cxx in (os.environ.get("CXX"), "g++", "/opt/rocm/lib/llvm/bin/clang++", "clang++"):
+        if cxx and shutil.which(cxx):
+            return cxx
+    raise AssertionError("no C++ compiler found")
+
+
+def test_shape_list_matches_synth():
+    """The program's copy of ALL_PU_SIZES is the package's list."""
+    import re
+    from nnfme import synth
+    text = open(SRC).read()
+    body = text[text.index("kShapes[][2] = {"):text.index("};", text.index("kShapes[][2] = {"))]
+    got = [(int(a), int(b)) for a, b in re.findall(r"\{(\d+), (\d+)\}", body)]
+    assert got == [tuple(s) for s in synth.ALL_PU_SIZES]
+
+
+def test_srv_pack_host_against_kernel_mapping(tmp_path):
+    exe = str(tmp_path / "test_srv_pack")
+    cxx = _compiler()
+    # the sanitizer runtimes linked statically (clang's default), so the program needs no preload
+    static = [] if "clang" in os.path.basename(cxx) else ["-static-libasan", "-static-libubsan"]
+    build = subprocess.run([cxx, *static, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer",
+                            "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
+                            "-I", INC, "-o", exe, SRC], capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stdout + build.stderr
+    env = dict(os.environ)
+    env["ASAN_OPTIONS"] = "detect_leaks=1:halt_on_error=1:abort_on_error=0"
+    env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    out = run.stdout + run.stderr
+    assert "AddressSanitizer" not in out and "runtime error:" not in out, out[-4000:]
+    assert run.returncode == 0, out[-4000:]
+    assert "srv pack ok: 48 shape x depth cases" in out, out[-2000:]

@@ -3,7 +3,11 @@
 (through ctypes, so a little above the C++ figure) against the server's device service time
 (fme_single_last_device_us): the difference is host + PCIe + polling.
 
-usage: python tools/single_probe.py [calls]"""
+usage: python tools/single_probe.py [calls] [--bit-depth {8,10}]
+
+--bit-depth 10: a 10-bit context and synth_luma_hbd pictures (the main10 configurations).  Only the
+Python ABI is used, so the same file measures any build of the library ($FME_LIB_PATH)."""
+import argparse
 import os
 import sys
 import time
@@ -17,12 +21,18 @@ sys.path.insert(0, os.path.join(ROOT, "hm16.9-nn_fme_amd"))
 def main():
     from nnfme import synth, weights
     from nnfme.runtime import FmeContext
-    calls = int(sys.argv[1]) if len(sys.argv) > 1 else 300
-    ctx = FmeContext(nn_mode=1, qp=22)
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("calls", nargs="?", type=int, default=300)
+    ap.add_argument("--bit-depth", type=int, choices=(8, 10), default=8)
+    args = ap.parse_args()
+    calls, bd = args.calls, args.bit_depth
+    ctx = FmeContext(nn_mode=1, qp=22, bit_depth=bd)
     ctx.load_nn(weights.load_weights(22))
     W, H, pad = 416, 240, 80
-    pic = np.pad(synth.synth_luma(W, H, 1).astype(np.int16), pad, mode="edge")
-    org = synth.synth_luma(W, H, 2).astype(np.int16)
+    luma = synth.synth_luma if bd == 8 else (lambda w, h, t: synth.synth_luma_hbd(w, h, t, bd))
+    pic = np.pad(luma(W, H, 1).astype(np.int16), pad, mode="edge")
+    org = luma(W, H, 2).astype(np.int16)
+    print(f"bit depth {bd}, {calls} calls per shape", flush=True)
     rng = np.random.default_rng(3)
     ml = 65536.0 * np.sqrt(synth.LDP_LAMBDA[22][0])
     for (w, h) in ((8, 8), (16, 16), (64, 64)):
