@@ -30,11 +30,12 @@ namespace {
 
 thread_local std::string g_last_error = "";
 
-// counts buffer: 25 class counts (+ invalid), 24 scatter cursors, 8 lane tile-queue heads; zeroed per
-// batch by one
-// hipMemsetAsync, padded to 64 words (256 B) so the runtime issues one fill kernel, not two
-constexpr int kCountWords = 64;
-static_assert(2 * kNumClasses + 1 + 8 <= kCountWords, "counter block");
+// counts buffer: two counter blocks of kCountWords (fme_device.h: 25 class counts (+ invalid), 24
+// scatter cursors, 8 lane tile-queue heads, the keyed-job count), both zeroed at allocation.  A
+// refinement batch counts in block counts_cur and its k_scatter zeroes the other one, which the
+// next batch uses: no fill dispatch per batch.  Whatever else touches the blocks (the integer
+// search, a batch whose launches failed midway) sets counts_dirty, and the next batch starts with
+// one hipMemsetAsync of both blocks (use_counts).
 
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -162,18 +163,20 @@ struct fme_ctx {
   DevBuf<fme_job> d_jobs;      // staging for fme_refine (host arrays)
   DevBuf<fme_result> d_res;
   DevBuf<fme_mv_result> d_mv;   // staging for fme_refine_mv
-  DevBuf<fme_job> d_pk_jobs;    // fme_refine*_packed_device: the unpacked batch
+  DevBuf<int32_t> koff;         // packed batches: key offset per keyed job (k_classify)
   DevBuf<uint8_t> cls;
   DevBuf<int32_t> perm;
   DevBuf<fme_job> sjobs;
-  DevBuf<int32_t> counts;      // 25 counts, 24 cursors, 24 tile-queue heads: one memset
+  DevBuf<int32_t> counts;      // two counter blocks (kCountWords each), used by alternate batches
+  int counts_cur = 0;          // the block the next batch counts in (zero unless counts_dirty)
+  bool counts_dirty = false;   // the blocks are not known to be zero: the next batch fills both
   DevBuf<int32_t> blk_agg;
   DevBuf<int32_t> blk_prefix;
   DevBuf<uint32_t> nn_state;   // 2 x 12 words
   int state_cur = 0;
   bool state_pending = false;   // reset / set_state not yet applied (next batch, stream order)
   uint32_t pending_state[12] = {};
-  DevBuf<Schedule> d_sched;     // built by k_schedule each batch
+  DevBuf<Schedule> d_sched;     // built by k_scatter each batch
   SchedParams sched_p{};
   int32_t* h_counts = nullptr; // pinned
 
@@ -256,7 +259,7 @@ struct fme_ctx {
 
   // Profiling: a ring of event sets, one per profiled batch, read once the batch has finished
   // (harvest_events), so profiling a run of batches adds no synchronisation.  Per set: 0 start,
-  // 1 classify end, 2 schedule end = scatter begin, 3 scatter end, 4 main search end, 5 search
+  // 1 classify end = scatter begin, (2 unused,) 3 scatter end, 4 main search end, 5 search
   // end, 6 batch end.
   static constexpr int kEv = 9;
   static constexpr int kEvSets = 32;
@@ -314,7 +317,8 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
   HIP_TRY(c->d_pics.reserve(FME_MAX_PICTURES));
   HIP_TRY(c->d_mlambda.reserve(FME_MAX_LAMBDAS));
   HIP_TRY(c->d_nn.reserve(kNnPkFloats));
-  HIP_TRY(c->counts.reserve(kCountWords));
+  HIP_TRY(c->counts.reserve(2 * kCountWords));
+  HIP_TRY(hipMemset(c->counts.p, 0, 2 * kCountWords * sizeof(int32_t)));
   HIP_TRY(c->d_sched.reserve(1));
   c->sched_p = sched_params();
   {
@@ -391,7 +395,7 @@ int fme_destroy(fme_ctx* c) {
   for (auto& e : c->ev_mc)
     if (e) (void)hipEventDestroy(e);
   c->d_pics.release(); c->d_mlambda.release(); c->d_keys.release(); c->d_nn.release(); c->d_net.release();
-  c->d_jobs.release(); c->d_res.release(); c->d_mv.release(); c->d_pk_jobs.release(); c->cls.release(); c->perm.release(); c->sjobs.release();
+  c->d_jobs.release(); c->d_res.release(); c->d_mv.release(); c->koff.release(); c->cls.release(); c->perm.release(); c->sjobs.release();
   c->counts.release(); c->blk_agg.release(); c->blk_prefix.release(); c->nn_state.release();
   c->d_sched.release();
   if (c->ev_done) (void)hipEventDestroy(c->ev_done);
@@ -687,7 +691,22 @@ static int ensure_work(fme_ctx* c, int n) {
   if (FME_SJOBS) HIP_TRY(c->sjobs.reserve(n));
   HIP_TRY(c->blk_agg.reserve(nb * 9));
   HIP_TRY(c->blk_prefix.reserve(nb * 9));
+  HIP_TRY(c->koff.reserve(n));
   return FME_OK;
+}
+
+// Before a batch's k_classify: the counter block it counts in is zero.  In steady state the
+// previous batch's k_scatter left it so; otherwise both blocks are filled here.  The blocks stay
+// marked dirty until the caller has enqueued every launch of the batch (counts_done).
+static int counts_begin(fme_ctx* c, hipStream_t s) {
+  if (c->counts_dirty) HIP_TRY(hipMemsetAsync(c->counts.p, 0, 2 * kCountWords * sizeof(int32_t), s));
+  c->counts_dirty = true;
+  return FME_OK;
+}
+// A refinement batch fully enqueued: its k_scatter zeroes the other block, which the next batch uses.
+static void counts_done(fme_ctx* c) {
+  c->counts_cur ^= 1;
+  c->counts_dirty = false;
 }
 
 static WorkBufs work_bufs(fme_ctx* c) {
@@ -695,9 +714,11 @@ static WorkBufs work_bufs(fme_ctx* c) {
   w.cls = c->cls.p;
   w.perm = c->perm.p;
   w.sjobs = c->sjobs.p;
-  w.counts = c->counts.p;
-  w.cursor = c->counts.p + kNumClasses + 1;
-  w.tile_ctr = c->counts.p + 2 * kNumClasses + 1;
+  w.koff = c->koff.p;
+  w.counts = c->counts.p + c->counts_cur * kCountWords;
+  w.counts_next = c->counts.p + (c->counts_cur ^ 1) * kCountWords;
+  w.cursor = w.counts + kNumClasses + 1;
+  w.tile_ctr = w.counts + 2 * kNumClasses + 1;
   w.blk_agg = c->blk_agg.p;
   w.blk_prefix = c->blk_prefix.p;
   w.nn_state = c->nn_state.p;
@@ -760,7 +781,7 @@ static int harvest_events(fme_ctx* c, bool wait_all) {
     }
     float* ms = c->last_ms;
     HIP_TRY(hipEventElapsedTime(&ms[0], e[0], e[1]));
-    HIP_TRY(hipEventElapsedTime(&ms[1], e[2], e[3]));
+    HIP_TRY(hipEventElapsedTime(&ms[1], e[1], e[3]));   // the scatter, which builds the schedule
     HIP_TRY(hipEventElapsedTime(&ms[2], e[3], e[5]));
     HIP_TRY(hipEventElapsedTime(&ms[3], e[5], e[6]));
     HIP_TRY(hipEventElapsedTime(&ms[4], e[0], e[6]));
@@ -778,9 +799,10 @@ static int harvest_events(fme_ctx* c, bool wait_all) {
 // cooperative AMP kernels beside them) -> NN + tail, all enqueued without waiting for the device.
 // Device validation covers what the host cannot see for device-resident jobs: a job with an
 // unknown PU shape, an unset picture / lambda slot or a key block outside the key buffer makes
-// k_schedule mark the batch rejected; every later kernel then skips its work.
+// k_scatter mark the batch rejected; every later kernel then skips its work.
+// d_jobs null: the batch is d_pjobs / d_key_base (fme_job_packed rows, read in place by every kernel).
 static int refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_result* d_mv, int n,
-                        hipStream_t s) {
+                        hipStream_t s, const fme_job_packed* d_pjobs = nullptr, const int32_t* d_key_base = nullptr) {
   if (c->cfg.nn_mode == 1 && !c->nn_loaded) return fail(FME_E_STATE, "fme_refine_device: nn_mode set but no weights loaded");
   if (c->cfg.nn_mode == 2 && !c->net_loaded) return fail(FME_E_STATE, "fme_refine_device: nn_mode 2 but no net loaded");
   if (c->cfg.nn_mode == 2 && c->nn_margin && n > c->nn_margin_cap)
@@ -797,6 +819,9 @@ static int refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fm
 
   BatchArgs a{};
   a.jobs = d_jobs;
+  a.pjobs = d_jobs ? nullptr : d_pjobs;
+  a.key_base = d_key_base;
+  a.koff = c->koff.p;
   a.res = d_res;
   a.keys = c->d_keys.p;
   a.n_keys = (int64_t)c->n_keys;
@@ -827,12 +852,11 @@ static int refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fm
     ev = c->ev[eb];
     HIP_TRY(hipEventRecord(ev[0], s));
   }
-  HIP_TRY(hipMemsetAsync(c->counts.p, 0, kCountWords * sizeof(int32_t), s));
+  rc = counts_begin(c, s);
+  if (rc) return rc;
   HIP_TRY(launch_classify(a, w, s));
   if (prof) HIP_TRY(hipEventRecord(ev[1], s));
-  HIP_TRY(launch_schedule(w, c->sched_p, s));
-  if (prof) HIP_TRY(hipEventRecord(ev[2], s));
-  HIP_TRY(launch_scatter(a, w, s));
+  HIP_TRY(launch_scatter(a, w, c->sched_p, s));
   if (prof) HIP_TRY(hipEventRecord(ev[3], s));
   if (c->ev_search) HIP_TRY(hipEventRecord(c->ev_search, s));
   // the lane kernel: every PU shape, one launch on the batch stream (8-bit); the pixel kernel at
@@ -858,6 +882,7 @@ static int refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fm
     c->ev_head++;
   }
   HIP_TRY(hipEventRecord(c->ev_done, s));
+  counts_done(c);
   c->batch_issued = true;
   if (a.nn_mode) c->state_cur ^= 1;
   return FME_OK;
@@ -966,14 +991,11 @@ static int refine_packed(fme_ctx* c, const fme_job_packed* d_jobs, const int32_t
   if (n < 0) return fail(FME_E_INVALID, "%s: n = %d", fn, n);
   if (n == 0) return FME_OK;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(c->d_pk_jobs.reserve(n));
   if (!d_res) {
     HIP_TRY(c->d_res.reserve(n));   // full records: context scratch
     d_res = c->d_res.p;
   }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(launch_unpack_jobs(d_jobs, d_key_base, c->d_pk_jobs.p, n, s));
-  return refine_batch(c, c->d_pk_jobs.p, d_res, d_mv, n, s);
+  return refine_batch(c, nullptr, d_res, d_mv, n, static_cast<hipStream_t>(stream), d_jobs, d_key_base);
 }
 
 int fme_refine_packed_device(fme_ctx* c, const fme_job_packed* d_jobs, const int32_t* d_key_base, fme_result* d_res,
@@ -1176,10 +1198,11 @@ static int tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t
       HIP_TRY(hipEventCreate(&c->ev_tz[1]));
     }
   }
-  HIP_TRY(hipMemsetAsync(c->counts.p, 0, kCountWords * sizeof(int32_t), s));
+  // the integer search fills its counter block itself and leaves both marked dirty (counts_begin)
+  c->counts_dirty = true;
+  HIP_TRY(hipMemsetAsync(w.counts, 0, kCountWords * sizeof(int32_t), s));
   HIP_TRY(launch_classify(a, w, s));
-  HIP_TRY(launch_schedule(w, c->sched_p, s));   // class offsets for the scatter
-  HIP_TRY(hipMemcpyAsync(c->h_counts, c->counts.p, kCountWords * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(c->h_counts, w.counts, kCountWords * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (c->h_counts[kNumClasses] > 0)
     return fail(FME_E_INVALID, "fme_integer_search_device: %d job(s) with an unsupported PU size or unset picture/lambda/key",
@@ -1196,7 +1219,7 @@ static int tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t
     off += cnt;
   }
   for (int q = 0; q < 3; q++) sc.prefix[q][kNumClasses] = nb[q];
-  HIP_TRY(launch_scatter(a, w, s));
+  HIP_TRY(launch_scatter(a, w, c->sched_p, s));   // with its own class offsets (the schedule goes unused)
   TzArgs ta{};
   ta.a = a;
   ta.sjobs = c->sjobs.p;

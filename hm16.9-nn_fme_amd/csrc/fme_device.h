@@ -48,6 +48,10 @@ __host__ __device__ __forceinline__ constexpr int lane_class_at(int pos) {
 constexpr int kBlock = 256;          // threads per workgroup (4 wavefronts)
 constexpr int kJobsPerScanBlock = 1024;  // classify / NN kernels: 4 jobs per thread
 constexpr int kKeyedWord = 60;           // counts[]: jobs that read a key block (k_classify)
+// One counter block: 25 class counts (+ invalid), 24 scatter cursors, 8 lane tile-queue heads, the
+// keyed-job count; padded to 64 words (256 B).  A context holds two, used by alternate batches.
+constexpr int kCountWords = 64;
+static_assert(2 * kNumClasses + 1 + 8 <= kKeyedWord && kKeyedWord < kCountWords, "counter block");
 
 // PU shape of each class (W, H).  Order: by area, then width.
 constexpr int kClassW[kNumClasses] = {4, 8, 8, 4, 16, 8, 16, 12, 16, 16, 8, 32,
@@ -122,7 +126,10 @@ hipError_t launch_bi_key(const BiKeyArgs& a, hipStream_t s);
 
 // One batch as the device sees it.
 struct BatchArgs {
-  const fme_job* jobs;
+  const fme_job* jobs;        // the batch as fme_job, or (packed entry points) null:
+  const fme_job_packed* pjobs;   // the caller's packed rows, read in place (load_job)
+  const int32_t* key_base;    // packed: key offset of each 64-job group's first keyed job, -1: none
+  const int32_t* koff;        // packed: key offset per job, keyed jobs' entries only (k_classify writes them)
   fme_result* res;
   const int16_t* keys;
   int64_t n_keys;
@@ -146,19 +153,21 @@ struct WorkBufs {
   int32_t* perm;         // [n] jobs grouped by class (original index)
   fme_job* sjobs;        // [n] copies of the jobs in class order (FME_SJOBS 1: the searches read
                          // them contiguously; 0: they read jobs[perm[i]] and k_scatter writes none)
+  int32_t* koff;         // [n] BatchArgs::koff as k_classify writes it (packed batches)
   int32_t* counts;       // [kNumClasses + 1]: per-class count, [24] = invalid jobs
+  int32_t* counts_next;  // the other counter block: k_scatter zeroes it for the next batch
   int32_t* cursor;       // [kNumClasses]
   int32_t* blk_agg;      // [nblk * 9] per-block max of the NN writer indices
   int32_t* blk_prefix;   // [nblk * 9] exclusive prefix (carry-in) per block
   uint32_t* nn_state;    // 2 x 12 words: slot[8], c, pu_h, pu_w, written
-  Schedule* sched;       // built on the device by k_schedule from counts
-  int32_t* tile_ctr;     // [8] lane-kernel tile queue heads (zeroed with counts)
+  Schedule* sched;       // built on the device by k_scatter (block 0) from counts
+  int32_t* tile_ctr;     // [8] lane-kernel tile queue heads (part of the counter block)
   fme_mv_result* mv_out; // compact per-job output (fme_refine_mv*), or null
 };
 // The search record of job i (the search writes its records in call order; the tail completes them).
 __device__ __forceinline__ const fme_result* search_rec(const BatchArgs& a, const WorkBufs&, int i) { return a.res + i; }
 
-// Schedule of the search kernel (k_schedule builds it on the device): class c's jobs are
+// Schedule of the search kernel (k_scatter builds it on the device): class c's jobs are
 // sjobs/perm[class_off[c] .. + class_cnt[c]) and its 64-lane wave tiles [prefix[c], prefix[c+1]).
 struct Schedule {
   int32_t prefix[kNumClasses + 1];
@@ -175,7 +184,7 @@ struct Schedule {
   int32_t pad_[3];
 };
 
-// What k_schedule needs to know about the search kernel: lanes per PU of each class (its unit
+// What k_scatter's schedule needs to know about the search kernel: lanes per PU of each class (its unit
 // count rounded up to a power of two).
 struct SchedParams {
   int32_t lanes[kNumClasses];
@@ -241,9 +250,9 @@ hipError_t launch_tz_levels(const TzArgs& ta, const TzChain& ch, const int32_t* 
 
 // Host-side launch helpers (fme_kernels.hip).
 hipError_t launch_classify(const BatchArgs& a, const WorkBufs& w, hipStream_t s);
-// one block: w.counts -> *w.sched (class offsets, block ranges, XCD queues, invalid count)
-hipError_t launch_schedule(const WorkBufs& w, const SchedParams& p, hipStream_t s);
-hipError_t launch_scatter(const BatchArgs& a, const WorkBufs& w, hipStream_t s);
+// every block: w.counts -> class offsets (LDS), jobs grouped by class; block 0 also writes *w.sched
+// (class offsets, block ranges, XCD queues, invalid count) and zeroes w.counts_next
+hipError_t launch_scatter(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, hipStream_t s);
 // 12 words of NN state written to dst in stream order (reset / set_state)
 hipError_t launch_put_state(uint32_t* dst, const uint32_t* v12, hipStream_t s);
 // the picture / lambda tables written in stream order from kernel arguments
@@ -319,10 +328,76 @@ hipError_t launch_gather_jobs(const fme_job* src, const fme_tz_ext* src_ext, con
                               fme_tz_ext* dst_ext, int n, hipStream_t s);
 hipError_t launch_nn_tail(const BatchArgs& a, const WorkBufs& w, const float* nn_params,
                           int state_in, hipStream_t s);
-// fme_job_packed -> fme_job (fme_refine*_packed_device): one lane per job, key offsets by a
-// per-wave scan from key_base[i / 64]
-hipError_t launch_unpack_jobs(const fme_job_packed* src, const int32_t* key_base, fme_job* dst, int n,
-                              hipStream_t s);
+
+// ---- the batch's jobs, either format -------------------------------------------------------------
+// Global pointers typed as such (global_load, not flat); 16-byte rows at their 4-byte alignment.
+typedef uint32_t job_u4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef __attribute__((address_space(1))) const job_u4 g_job_u4;
+typedef __attribute__((address_space(1))) const uint32_t g_job_u32;
+typedef __attribute__((address_space(1))) const int32_t g_job_i32;
+
+// fme_job_packed row (pu, ctl, mv, mvp words) -> fme_job, as fme_unpack_jobs (fme_api.cpp) does:
+// the range words are the canonical mv -/+ range bit, which gives the EMI step's four tests
+// (xTZ8PointSquareSearch, TEncSearch.cpp:1341-1376) the packed answers.  key_offset: the job's key
+// offset when its keyed bit is set (ignored otherwise).
+__device__ __forceinline__ bool packed_keyed(uint32_t ctl) { return ((ctl >> 21) & 1u) != 0; }
+__device__ __forceinline__ fme_job expand_job(job_u4 p, int32_t key_offset) {
+  const uint32_t pu = p.x, ctl = p.y;
+  const uint32_t rg = (ctl >> 22) & 15u;
+  const int16_t mv_x = (int16_t)(p.z & 0xFFFFu), mv_y = (int16_t)(p.z >> 16);
+  fme_job j;
+  j.x = (uint16_t)((pu & 2047u) * 4u);
+  j.y = (uint16_t)(((pu >> 11) & 2047u) * 4u);
+  j.w = (uint8_t)((((pu >> 22) & 15u) + 1u) * 4u);
+  j.h = (uint8_t)((((pu >> 26) & 15u) + 1u) * 4u);
+  j.org_id = (uint8_t)(ctl & 63u);
+  j.ref_id = (uint8_t)((ctl >> 6) & 63u);
+  j.lambda_id = (uint8_t)((ctl >> 12) & 31u);
+  j.flags = (uint8_t)((ctl >> 17) & 15u);
+  j.bits_in = (uint16_t)(ctl >> 26);
+  j.mv_x = mv_x;
+  j.mv_y = mv_y;
+  j.mvp_x = (int16_t)(p.w & 0xFFFFu);
+  j.mvp_y = (int16_t)(p.w >> 16);
+  j.lt_x = (int16_t)(mv_x - ((rg & FME_PK_RANGE_LEFT) ? 1 : 0));
+  j.rb_x = (int16_t)(mv_x + ((rg & FME_PK_RANGE_RIGHT) ? 1 : 0));
+  j.lt_y = (int16_t)(mv_y - ((rg & FME_PK_RANGE_TOP) ? 1 : 0));
+  j.rb_y = (int16_t)(mv_y + ((rg & FME_PK_RANGE_BOTTOM) ? 1 : 0));
+  j.key_offset = packed_keyed(ctl) ? key_offset : -1;
+  return j;
+}
+__device__ __forceinline__ job_u4 packed_row(const BatchArgs& a, int i) { return *((g_job_u4*)a.pjobs + i); }
+
+// Job i of the batch in registers: the caller's packed row expanded (one 16-byte load, and the key
+// offset k_classify wrote for a keyed job), or the fme_job itself (two 16-byte loads).  Which of
+// the two is a kernel argument, so the branch is wave-uniform.
+__device__ __forceinline__ fme_job load_job(const BatchArgs& a, int i) {
+  if (a.pjobs) {
+    const job_u4 p = packed_row(a, i);
+    int32_t ko = -1;
+    if (packed_keyed(p.y)) ko = ((g_job_i32*)a.koff)[i];
+    return expand_job(p, ko);
+  }
+  g_job_u4* const src = (g_job_u4*)(a.jobs + i);
+  const job_u4 q0 = src[0], q1 = src[1];
+  const uint32_t tmp[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+  fme_job j;
+  __builtin_memcpy(&j, tmp, sizeof(j));
+  return j;
+}
+static_assert(sizeof(fme_job) == 32 && sizeof(fme_job_packed) == 16, "job layouts");
+// PU size of job i alone (the tails' stale C / PU-size writer)
+__device__ __forceinline__ void load_job_wh(const BatchArgs& a, int i, uint32_t& w, uint32_t& h) {
+  if (a.pjobs) {
+    const uint32_t pu = *(g_job_u32*)&a.pjobs[i].pu;
+    w = (((pu >> 22) & 15u) + 1u) * 4u;
+    h = (((pu >> 26) & 15u) + 1u) * 4u;
+  } else {
+    const uint32_t q = ((g_job_u32*)(a.jobs + i))[1];   // w, h, org_id, ref_id
+    w = q & 0xFFu;
+    h = (q >> 8) & 0xFFu;
+  }
+}
 
 // The tail kernels' output: xMotionEstimation's MV / cost / bits with the NN class and status,
 // into the full record or, for fme_refine_mv*, the compact one alone.

@@ -1,9 +1,17 @@
 // fme_kernels.hip — CDNA4 (gfx950) kernels of the fractional-pel motion-estimation path.
 //
-// One batch of PU jobs runs as:
-//   classify   per job: PU-shape class, EMI push count; per block: class histogram and the
-//              max of the NN "last writer" indices (first pass of a prefix-max scan).
-//   scatter    jobs grouped by class (block-aggregated atomics), giving the search tiles.
+// One batch of PU jobs runs as five launches (tables, classify, scatter, search, nn_tail).  The
+// jobs are read where the caller put them, through load_job (fme_device.h): fme_job rows, or the
+// 16-byte fme_job_packed rows of the packed entry points expanded in registers; no kernel writes
+// an unpacked copy.
+//   classify   per job: validation, PU-shape class, EMI push count, and for packed rows the keyed
+//              jobs' key offsets (a scan per 64-job group from key_base); per block: class
+//              histogram and the max of the NN "last writer" indices (first pass of a prefix-max
+//              scan).
+//   scatter    the schedule from the histogram (class offsets in every block; block 0 publishes
+//              the search's tile ranges and per-XCD queues), jobs grouped by class
+//              (block-aggregated atomics), and the other counter block zeroed for the next batch,
+//              which therefore needs no fill dispatch.
 //   search     EMI square step + FracDIF per tile of same-shape PUs (fme_search.hip).
 //   nn_tail    prefix-max over jobs resolves which earlier job last wrote each array_e slot
 //              (the reference's stale global state, TEncSearch.cpp:55-57, 198-201), then
@@ -96,10 +104,45 @@ __global__ __launch_bounds__(kBlock) void k_classify(BatchArgs a, WorkBufs w) {
   const int tid = threadIdx.x;
   const int base = blockIdx.x * kJobsPerScanBlock;
   fme_job jb[Q];
+  if (a.pjobs) {
+    // Packed rows: a wave's 64 lanes hold one 64-job group (base and q * kBlock are multiples of
+    // 64), whose keyed blocks follow key_base[group] densely in job order, so a job's key offset
+    // is the base plus the exclusive sum of w*h over the group's earlier keyed jobs.  Groups
+    // without a keyed job (every group of a uni-pred batch) scan and write nothing.
+    job_u4 row[Q];
 #pragma unroll
-  for (int q = 0; q < Q; q++) {
-    const int i = base + q * kBlock + tid;
-    if (i < a.n) jb[q] = a.jobs[i];
+    for (int q = 0; q < Q; q++) {
+      const int i = base + q * kBlock + tid;
+      row[q] = job_u4{0u, 0u, 0u, 0u};
+      if (i < a.n) row[q] = packed_row(a, i);
+    }
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+      const int i = base + q * kBlock + tid;
+      const bool keyed_q = i < a.n && packed_keyed(row[q].y);
+      int ko = -1;
+      if (__ballot(keyed_q)) {   // wave-uniform
+        const int wh = (int)((((row[q].x >> 22) & 15u) + 1u) * 4u) * (int)((((row[q].x >> 26) & 15u) + 1u) * 4u);
+        const int lane = tid & 63;
+        int s = keyed_q ? wh : 0;   // inclusive scan over the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const int o = __shfl_up(s, off, 64);
+          if (lane >= off) s += o;
+        }
+        if (keyed_q) {
+          ko = a.key_base[i >> 6] + s - wh;
+          w.koff[i] = ko;
+        }
+      }
+      jb[q] = expand_job(row[q], ko);
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+      const int i = base + q * kBlock + tid;
+      if (i < a.n) jb[q] = load_job(a, i);
+    }
   }
   __shared__ int32_t keys_bad, keyed;
   if (tid == 0) {
@@ -160,27 +203,33 @@ __global__ __launch_bounds__(kBlock) void k_classify(BatchArgs a, WorkBufs w) {
 }
 
 // ---------------------------------------------------------------------------------------
-// schedule: the class histogram -> class offsets, each search kernel's block ranges and the
-// lane kernels' per-XCD tile queues, all on the device (one wave, one lane per class), so a
-// batch needs no host round trip between classify and search.
+// scatter, with the schedule: the class histogram -> class offsets, the search kernel's block
+// ranges and the lane kernels' per-XCD tile queues, all on the device, so a batch needs no host
+// round trip between classify and search.  Every block scans the 24 counts for the class offsets
+// it scatters to (one wave, one lane per class); block 0 goes on to write the whole Schedule,
+// which only kernels after the scatter read, and zeroes the other counter block for the next batch.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ int wave_excl_scan(int v) {
+  const int lane = (int)threadIdx.x & 63;
   int s = v;
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {
     const int o = __shfl_up(s, off, 64);
-    if ((int)threadIdx.x >= off) s += o;
+    if (lane >= off) s += o;
   }
   return s - v;
 }
 
-__global__ __launch_bounds__(64) void k_schedule(WorkBufs w, SchedParams p) {
-  const int c = threadIdx.x;
-  Schedule* sc = w.sched;
-  const int inv = w.counts[kNumClasses];
-  const int cnt = (c < kNumClasses && inv == 0) ? w.counts[c] : 0;
-  const int nb = cnt > 0 ? (int)(((long long)cnt * p.lanes[c] + 63) / 64) : 0;   // 64-lane wave tiles
+// Lane c < kNumClasses of one wave: class c's count; returns its offset in class order.
+// publish: also write *sc (block ranges, XCD queues, the invalid count).
+__device__ __forceinline__ int build_schedule(const int32_t* __restrict__ counts, const SchedParams& p, Schedule* sc,
+                                              bool publish) {
+  const int c = (int)threadIdx.x & 63;
+  const int inv = counts[kNumClasses];
+  const int cnt = (c < kNumClasses && inv == 0) ? counts[c] : 0;
   const int off = wave_excl_scan(cnt);
+  if (!publish) return off;   // wave-uniform
+  const int nb = cnt > 0 ? (int)(((long long)cnt * p.lanes[c < kNumClasses ? c : 0] + 63) / 64) : 0;   // 64-lane wave tiles
   if (c < kNumClasses) {
     sc->class_off[c] = off;
     sc->class_cnt[c] = cnt;
@@ -206,15 +255,12 @@ __global__ __launch_bounds__(64) void k_schedule(WorkBufs w, SchedParams p) {
     }
   }
   if (c == 0) sc->invalid = inv;
+  return off;
 }
 
-__global__ __launch_bounds__(kBlock) void k_scatter(BatchArgs a, WorkBufs w) {
-  __shared__ int32_t cnt[kNumClasses], basep[kNumClasses];
-  const Schedule* __restrict__ sc = w.sched;
-  if (sc->invalid) return;   // rejected batch: nothing downstream reads the grouping
+__global__ __launch_bounds__(kBlock) void k_scatter(BatchArgs a, WorkBufs w, SchedParams sp) {
+  __shared__ int32_t cnt[kNumClasses], basep[kNumClasses], class_off[kNumClasses];
   const int tid = threadIdx.x;
-  if (tid < kNumClasses) cnt[tid] = 0;
-  __syncthreads();
   const int base = blockIdx.x * kJobsPerScanBlock;
   int rank[kJobsPerScanBlock / kBlock];
   int cls[kJobsPerScanBlock / kBlock];
@@ -225,9 +271,18 @@ __global__ __launch_bounds__(kBlock) void k_scatter(BatchArgs a, WorkBufs w) {
     cls[q] = 255;
     if (i < a.n) {
       cls[q] = w.cls[i];
-      if (FME_SJOBS) jb[q] = a.jobs[i];
+      if (FME_SJOBS) jb[q] = load_job(a, i);
     }
   }
+  if (tid < 64) {
+    const int off = build_schedule(w.counts, sp, w.sched, blockIdx.x == 0);
+    if (tid < kNumClasses) class_off[tid] = off;
+  } else if (blockIdx.x == 0 && tid < 64 + kCountWords) {
+    w.counts_next[tid - 64] = 0;   // the next batch's counter block (also when this one is rejected)
+  }
+  if (w.counts[kNumClasses]) return;   // rejected batch: nothing downstream reads the grouping
+  if (tid < kNumClasses) cnt[tid] = 0;
+  __syncthreads();
 #pragma unroll
   for (int q = 0; q < kJobsPerScanBlock / kBlock; q++)
     if (cls[q] < kNumClasses) rank[q] = atomicAdd(&cnt[cls[q]], 1);
@@ -238,7 +293,7 @@ __global__ __launch_bounds__(kBlock) void k_scatter(BatchArgs a, WorkBufs w) {
   for (int q = 0; q < kJobsPerScanBlock / kBlock; q++) {
     const int i = base + q * kBlock + tid;
     if (cls[q] < kNumClasses) {
-      const int dst = sc->class_off[cls[q]] + basep[cls[q]] + rank[q];
+      const int dst = class_off[cls[q]] + basep[cls[q]] + rank[q];
       w.perm[dst] = i;
       if (FME_SJOBS) w.sjobs[dst] = jb[q];
     }
@@ -421,8 +476,7 @@ __device__ __forceinline__ void tail_job(const BatchArgs& a, const WorkBufs& w, 
       written |= 0x100u;
     } else if (src[8] >= 0) {
       c = search_rec(a, w, src[8])->c;
-      ph = a.jobs[src[8]].h;
-      pw = a.jobs[src[8]].w;
+      load_job_wh(a, src[8], pw, ph);
       written |= 0x100u;
     } else {
       c = st_in[8];
@@ -490,7 +544,7 @@ void k_nn_tail(BatchArgs a, WorkBufs w, const float* __restrict__ nnp_g, int sta
     // usually the job's own pushes)
     u32x4 r0{}, r1{}, r2{}, r3{};
     if (valid) {
-      j = a.jobs[i];
+      j = load_job(a, i);
       const u32x4* rb = reinterpret_cast<const u32x4*>(search_rec(a, w, i));
       r0 = rb[0];
       r1 = rb[1];
@@ -557,13 +611,8 @@ hipError_t launch_put_state(uint32_t* dst, const uint32_t* v12, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_schedule(const WorkBufs& w, const SchedParams& p, hipStream_t s) {
-  hipLaunchKernelGGL(k_schedule, dim3(1), dim3(64), 0, s, w, p);
-  return hipGetLastError();
-}
-
-hipError_t launch_scatter(const BatchArgs& a, const WorkBufs& w, hipStream_t s) {
-  hipLaunchKernelGGL(k_scatter, dim3(nblocks(a.n)), dim3(kBlock), 0, s, a, w);
+hipError_t launch_scatter(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, hipStream_t s) {
+  hipLaunchKernelGGL(k_scatter, dim3(nblocks(a.n)), dim3(kBlock), 0, s, a, w, p);
   return hipGetLastError();
 }
 
@@ -625,61 +674,6 @@ hipError_t launch_download(const void* src, void* dst, size_t n16, int wgs, hipS
   const int g = (int)std::min<long>(wgs, std::max<long>(need, 1));
   hipLaunchKernelGGL(k_download, dim3(g), dim3(kDlThreads), 0, s, static_cast<const u32x4*>(src),
                      static_cast<u32x4*>(dst), (long)n16);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// packed jobs (fme_job_packed, include/fme.h) -> fme_job.  Lane i unpacks job i; a wave is 64
-// consecutive jobs, whose keyed blocks follow key_base[wave] densely in job order, so each lane's
-// key offset is the base plus the exclusive sum of w*h over the wave's earlier keyed jobs.  The
-// range words are the canonical mv -/+ range bit, which gives the EMI step's four tests
-// (xTZ8PointSquareSearch, TEncSearch.cpp:1341-1376) the packed answers.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_unpack_jobs(const fme_job_packed* __restrict__ src,
-                                                       const int32_t* __restrict__ key_base,
-                                                       fme_job* __restrict__ dst, int n) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  fme_job_packed p{};
-  if (i < n) p = src[i];
-  const uint32_t pu = p.pu, ctl = p.ctl;
-  const int w = (int)(((pu >> 22) & 15u) + 1u) * 4, h = (int)(((pu >> 26) & 15u) + 1u) * 4;
-  const bool keyed = i < n && ((ctl >> 21) & 1u);
-  const int lane = (int)(threadIdx.x & 63);
-  int s = keyed ? w * h : 0;   // inclusive scan over the wave
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(s, off, 64);
-    if (lane >= off) s += o;
-  }
-  if (i >= n) return;
-  const int base = key_base[i >> 6];
-  fme_job j;
-  j.x = (uint16_t)((pu & 2047u) * 4u);
-  j.y = (uint16_t)(((pu >> 11) & 2047u) * 4u);
-  j.w = (uint8_t)w;
-  j.h = (uint8_t)h;
-  j.org_id = (uint8_t)(ctl & 63u);
-  j.ref_id = (uint8_t)((ctl >> 6) & 63u);
-  j.lambda_id = (uint8_t)((ctl >> 12) & 31u);
-  j.flags = (uint8_t)((ctl >> 17) & 15u);
-  const uint32_t rg = (ctl >> 22) & 15u;
-  j.bits_in = (uint16_t)(ctl >> 26);
-  j.mv_x = p.mv_x;
-  j.mv_y = p.mv_y;
-  j.mvp_x = p.mvp_x;
-  j.mvp_y = p.mvp_y;
-  j.lt_x = (int16_t)(p.mv_x - ((rg & FME_PK_RANGE_LEFT) ? 1 : 0));
-  j.rb_x = (int16_t)(p.mv_x + ((rg & FME_PK_RANGE_RIGHT) ? 1 : 0));
-  j.lt_y = (int16_t)(p.mv_y - ((rg & FME_PK_RANGE_TOP) ? 1 : 0));
-  j.rb_y = (int16_t)(p.mv_y + ((rg & FME_PK_RANGE_BOTTOM) ? 1 : 0));
-  j.key_offset = keyed ? base + s - w * h : -1;
-  dst[i] = j;
-}
-
-hipError_t launch_unpack_jobs(const fme_job_packed* src, const int32_t* key_base, fme_job* dst, int n,
-                              hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_unpack_jobs, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, src, key_base, dst, n);
   return hipGetLastError();
 }
 

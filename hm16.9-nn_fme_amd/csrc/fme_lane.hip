@@ -878,12 +878,14 @@ __device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* 
   FME_STAMP(0);
   const int jid = perm[cls_off + p];
   fme_job j;
-  {   // two 16-byte global loads (a struct copy through an address-space-1 pointer does not compile
-      // in the host pass): the class-ordered copy, or (FME_SJOBS 0) the caller's job by its index
-    g_job* const src = FME_SJOBS ? sjobs + cls_off + p : (g_job*)a.jobs + jid;
+  if (FME_SJOBS) {   // two 16-byte global loads (a struct copy through an address-space-1 pointer does
+                     // not compile in the host pass): the class-ordered copy
+    g_job* const src = sjobs + cls_off + p;
     const u32x4a q0 = *(gu4*)src, q1 = *(gu4*)((g_u8*)src + 16);
     uint32_t tmp[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
     __builtin_memcpy(&j, tmp, sizeof(j));
+  } else {           // the caller's job by its index: a packed row expanded, or the fme_job
+    j = load_job(a, jid);
   }
   // The reference's descriptor is read from LDS where a window is loaded (an opaque index keeps
   // the compiler from holding the 40-byte copy in registers, or scratch, across the passes).

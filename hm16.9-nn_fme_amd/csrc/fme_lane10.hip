@@ -492,13 +492,7 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
   const int ux = uu % UX, uy = uu / UX;
 
   const int jid = perm[cls_off + p];
-  fme_job j;
-  {
-    g_job* const src = (g_job*)a.jobs + jid;
-    const u32x4a q0 = *(gu4*)src, q1 = *(gu4*)((const __attribute__((address_space(1))) uint8_t*)src + 16);
-    uint32_t tmp[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-    __builtin_memcpy(&j, tmp, sizeof(j));
-  }
+  const fme_job j = load_job(a, jid);
   auto ref_pic = [&]() FME_AI -> PicDesc {
     int rid = j.ref_id;
     asm volatile("" : "+v"(rid));
@@ -755,7 +749,7 @@ __device__ __forceinline__ int xcc_id() { return __builtin_amdgcn_s_getreg((20) 
 
 }  // namespace
 
-// The 8-bit lane kernel's classes and unit shapes (fme_lane.hip; k_schedule's tile layout is
+// The 8-bit lane kernel's classes and unit shapes (fme_lane.hip; the schedule's tile layout is
 // sched_params(), shared): 4x8 units, 4x4 units for 8x4 / 16x4 / 16x12.
 #define FME_L10_CLASSES(X)                                                                           \
   X(0, 4, 8, 4, 8) X(3, 4, 16, 4, 8) X(1, 8, 4, 4, 4) X(4, 16, 4, 4, 4) X(2, 8, 8, 4, 8)              \

@@ -332,7 +332,7 @@ __global__ __launch_bounds__(kRound) void k_nn_deep_tail(BatchArgs a, WorkBufs w
     const bool valid = i < a.n;
     if (!__syncthreads_or(valid)) break;
     fme_job j{};
-    if (valid) j = a.jobs[i];
+    if (valid) j = load_job(a, i);
     // writer indices of this job, prefix-max over the round (carry from earlier rounds/blocks)
     int run[9];
     const bool wr = valid && nn_writes_c(j);
@@ -378,8 +378,7 @@ __global__ __launch_bounds__(kRound) void k_nn_deep_tail(BatchArgs a, WorkBufs w
     uint32_t c = st_in[8], ph = st_in[9], pw = st_in[10];
     if (src[8] >= 0 && valid) {
       c = search_rec(a, w, src[8])->c;
-      ph = a.jobs[src[8]].h;
-      pw = a.jobs[src[8]].w;
+      load_job_wh(a, src[8], pw, ph);
       written |= 0x100u;
     }
     T in[17];

@@ -256,7 +256,7 @@ __global__ __launch_bounds__(kPxNT) void k_search_px(BatchArgs a, WorkBufs wb) {
   // the PUs wider or taller than 16 (class order from k_scatter; k_search_px_wave takes the rest)
   for (int q = wb.sched->class_off[kPxSmallClasses] + (int)blockIdx.x; q < a.n; q += gridDim.x) {
     const int i = wb.perm[q];
-    const fme_job j = a.jobs[i];
+    const fme_job j = load_job(a, i);
     const int w = j.w, h = j.h, ws = w + 10, wh = h + 10;
     // ---- 1. window and key -------------------------------------------------------------------
     {
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(kPxNT) __attribute__((amdgpu_waves_per_eu(FME_PXW_W
   const int n_small = wb.sched->class_off[kPxSmallClasses];
   for (int q = (int)blockIdx.x * kPxWaves + wid; q < n_small; q += (int)gridDim.x * kPxWaves) {
     const int i = __builtin_amdgcn_readfirstlane(wb.perm[q]);
-    const fme_job j = a.jobs[i];
+    const fme_job j = load_job(a, i);
     const int w = j.w, h = j.h, ws = w + 10, wh = h + 10;
     // ---- 1. window and key (rows of the window per pass: 64 / ws) ----
     {

@@ -374,9 +374,12 @@ int fme_refine_mv_device(fme_ctx* ctx, const fme_job* d_jobs, fme_mv_result* d_o
 /* Packed jobs (fme_job_packed).  fme_pack_jobs: host, n jobs -> out[n] and key_base[ceil(n/64)]
  * (pure host code, no context).  fme_unpack_jobs: the inverse, giving each job's canonical
  * fme_job (range words mv -/+ the range bits, key_offset -1 for unkeyed jobs); the device path
- * unpacks the same way.  fme_refine_packed_device / fme_refine_mv_packed_device: the device
- * batch of fme_refine_device / fme_refine_mv_device over device-resident packed jobs (a 16-byte
- * read and a 32-byte write per job in HBM before classify), identical results.               */
+ * expands a row the same way.  fme_refine_packed_device / fme_refine_mv_packed_device: the device
+ * batch of fme_refine_device / fme_refine_mv_device over device-resident packed jobs, identical
+ * results.  Every kernel of the batch reads the caller's 16-byte rows in place and expands them
+ * in registers (no unpacked copy is written); the key offset of a keyed job is scanned per 64-job
+ * group by the classify kernel.  The rows and key_base must stay valid and unchanged until the
+ * batch has finished, as the jobs of fme_refine_device must.                                  */
 int fme_pack_jobs(const fme_job* jobs, int n, fme_job_packed* out, int32_t* key_base);
 int fme_unpack_jobs(const fme_job_packed* packed, const int32_t* key_base, int n, fme_job* out);
 int fme_refine_packed_device(fme_ctx* ctx, const fme_job_packed* d_jobs, const int32_t* d_key_base,
