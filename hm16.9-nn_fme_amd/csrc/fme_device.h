@@ -1,5 +1,5 @@
 // fme_device.h — types shared by the HIP kernels (fme_kernels.hip) and the host runtime
-// (fme_api.cpp).  Not part of the public ABI (include/fme.h is).
+// (fme_api.cpp, fme_producers.cpp).  Not part of the public ABI (include/fme.h is).
 #pragma once
 
 #include <hip/hip_runtime.h>
