@@ -151,6 +151,16 @@ struct fme_ctx {
   fme::DevBuf<fme_wp_param> d_mc_wp;
   hipEvent_t ev_mc[2] = {nullptr, nullptr};
   bool mc_timed = false;
+  // prediction error / merge estimation (fme_merge.cpp): staging for the host entry points, the
+  // skipped-task counter, the stream of the last launch, timing events
+  fme::DevBuf<fme_pe_task> d_pe_tasks;
+  fme::DevBuf<uint32_t> d_pe_dist;
+  fme::DevBuf<int32_t> d_pe_invalid;
+  std::vector<fme_pe_task> h_pe_tasks;
+  std::vector<uint32_t> h_pe_dist;
+  hipStream_t pe_stream = nullptr;
+  hipEvent_t ev_pe[2] = {nullptr, nullptr};
+  bool pe_timed = false;
   // integer search: staging for the host entry point, timing events
   fme::DevBuf<fme_tz_ext> d_tz_ext;
   fme::DevBuf<uint32_t> d_tz_sad;

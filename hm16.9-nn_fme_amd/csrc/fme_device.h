@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/fme.h"
+#include "../../include/fme_merge.h"
 #include "fme_srv_pack.h"
 
 // 0 (default): k_scatter writes only the permutation and the searches gather jobs[perm[i]];
@@ -122,6 +123,19 @@ struct BiKeyArgs {
   int32_t bit_depth;          // 8, or 10: uint16 planes, ClipForBiPredMe to 0..1023 (k_bi_key<10>)
 };
 hipError_t launch_bi_key(const BiKeyArgs& a, hipStream_t s);
+
+// One prediction-error launch (fme_merge.hip k_pred_err): xGetInterPredictionError per task, the
+// luma prediction of the task's motion and its SATD / SAD against the original.
+struct PeArgs {
+  const fme_pe_task* tasks;
+  const PicDesc* pics;
+  uint32_t* dist;             // per task; 0xFFFFFFFF for a skipped (invalid) one
+  int32_t* invalid;           // count of skipped tasks
+  int32_t n;
+  int32_t bit_depth;          // 8, or 10: uint16 planes, the PU's sum >> 2
+  int32_t use_hadamard;       // HADME (fme_config.use_hadamard)
+};
+hipError_t launch_pred_err(const PeArgs& a, hipStream_t s);
 
 
 // One batch as the device sees it.

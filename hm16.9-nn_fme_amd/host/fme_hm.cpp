@@ -253,6 +253,22 @@ void MotionCompensator::run(uint8_t* y, int ys, uint8_t* cb, uint8_t* cr, int cs
   jobs_.clear();
 }
 
+// ---- MergeEstimator -----------------------------------------------------------------------
+
+int MergeEstimator::add(const fme_merge_req& req) {
+  reqs_.push_back(req);
+  return (int)reqs_.size() - 1;
+}
+
+std::vector<fme_merge_res> MergeEstimator::run() {
+  std::vector<fme_merge_res> res(reqs_.size());
+  std::lock_guard<std::mutex> lk(search_.mutex());
+  if (!reqs_.empty())
+    check(fme_merge_estimate(search_.ctx(), reqs_.data(), res.data(), (int)reqs_.size(), nullptr), "fme_merge_estimate");
+  reqs_.clear();
+  return res;
+}
+
 // ---- InterSearchP -------------------------------------------------------------------------
 
 int InterSearchP::add(const fme_pu_req& req) {

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "fme.h"
+#include "fme_merge.h"
 
 namespace fme_hm {
 
@@ -153,6 +154,24 @@ class MotionCompensator {
   std::vector<fme_mc_job> jobs_;
   std::vector<uint8_t> stage_;
   std::vector<uint16_t> stage16_;
+};
+
+// The part of predInterSearch's PU loop between the uni / bi decision and the final
+// motionCompensation (TEncSearch.cpp:4110-4172; include/fme_merge.h): per non-2Nx2N PU
+// xGetInterPredictionError of the ME result, xMergeEstimation over the caller's merge candidates
+// (TComDataCU::getInterMergeCandidates) and the uiMRGCost < uiMECost choice.  The caller queues one
+// fme_merge_req per PU (a CTU row's or a frame's) and gets one fme_merge_res per request; the depth
+// is the search's (SearchConfig::bitDepth), the pictures those of setPicture* / setPictureYuv*.
+class MergeEstimator {
+ public:
+  explicit MergeEstimator(FracSearch& search) : search_(search) {}
+  int add(const fme_merge_req& req);     // index of the request in the pending batch
+  int pending() const { return (int)reqs_.size(); }
+  std::vector<fme_merge_res> run();      // the queued requests in order; clears the queue
+
+ private:
+  FracSearch& search_;
+  std::vector<fme_merge_req> reqs_;
 };
 
 // TEncSearch::predInterSearch's uni-directional PU / reference loop for P slices
