@@ -161,6 +161,15 @@ struct fme_ctx {
   hipStream_t pe_stream = nullptr;
   hipEvent_t ev_pe[2] = {nullptr, nullptr};
   bool pe_timed = false;
+  // skip check (fme_skip.cpp): the same for the SSE launch
+  fme::DevBuf<fme_sse_task> d_sse_tasks;
+  fme::DevBuf<uint32_t> d_sse_out;       // [n][3]
+  fme::DevBuf<int32_t> d_sse_invalid;
+  std::vector<fme_sse_task> h_sse_tasks;
+  std::vector<uint32_t> h_sse_out;
+  hipStream_t sse_stream = nullptr;
+  hipEvent_t ev_sse[2] = {nullptr, nullptr};
+  bool sse_timed = false;
   // integer search: staging for the host entry point, timing events
   fme::DevBuf<fme_tz_ext> d_tz_ext;
   fme::DevBuf<uint32_t> d_tz_sad;

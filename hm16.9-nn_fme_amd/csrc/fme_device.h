@@ -7,6 +7,7 @@
 
 #include "../../include/fme.h"
 #include "../../include/fme_merge.h"
+#include "../../include/fme_skip.h"
 #include "fme_srv_pack.h"
 
 // 0 (default): k_scatter writes only the permutation and the searches gather jobs[perm[i]];
@@ -136,6 +137,18 @@ struct PeArgs {
   int32_t use_hadamard;       // HADME (fme_config.use_hadamard)
 };
 hipError_t launch_pred_err(const PeArgs& a, hipStream_t s);
+
+// One skip-check launch (fme_skip.hip k_pred_sse): the Y, Cb and Cr prediction of each task's
+// motion and the three SSEs against the original (getDistPart with DF_SSE).
+struct SseArgs {
+  const fme_sse_task* tasks;
+  const PicDesc* pics;
+  uint32_t* sse;              // [n][3] Y, Cb, Cr; 0xFFFFFFFF x 3 for a skipped (invalid) task
+  int32_t* invalid;           // count of skipped tasks
+  int32_t n;
+  int32_t bit_depth;          // 8, or 10: uint16 planes, each sample's square >> 4
+};
+hipError_t launch_pred_sse(const SseArgs& a, hipStream_t s);
 
 
 // One batch as the device sees it.

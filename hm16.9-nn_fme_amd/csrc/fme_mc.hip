@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fme_device.h"
+#include "fme_mc_chroma.h"
 #include "fme_mc_luma.h"
 #include "fme_simd.h"
 
@@ -28,7 +29,7 @@ namespace fme {
 namespace {
 
 using namespace simd;
-using namespace mcl;   // taps, clip_mv, UnitWin, pred10 (shared with fme_merge.hip)
+using namespace mcl;   // taps, clip_mv, UnitWin, pred10, chroma_pred8 / 10 (shared with fme_merge.hip, fme_skip.hip)
 
 __device__ __forceinline__ bool mc_job_valid(const McArgs& a, const fme_mc_job& j) {
   if (j.w < 4 || j.h < 4 || j.w > 64 || j.h > 64 || (j.w & 3) || (j.h & 3)) return false;
@@ -214,11 +215,7 @@ __global__ __launch_bounds__(kMcBlock) void k_mc(McArgs a) {
 #pragma unroll
       for (int k = 0; k < 2; k++) {
         if (k >= in.nl) break;
-        const PicDesc& p = in.pic[k];
-        const Plane pl{comp == 1 ? p.cb : p.cr, p.cstride, p.width >> 1, p.height >> 1};
-        UnitWin<4, 2> w;
-        w.load(pl, ((p.cstride | (int)(uintptr_t)pl.p) & 3) == 0, x + in.cix[k], y + in.ciy[k]);
-        w.pred(chroma_taps(in.cfx[k]), 0u, chroma_taps(in.cfy[k]), 0u, uni, o);
+        chroma_pred8(in.pic[k], comp, x + in.cix[k], y + in.ciy[k], in.cfx[k], in.cfy[k], uni, o);
 #pragma unroll
         for (int r = 0; r < 2; r++)
 #pragma unroll
@@ -344,10 +341,7 @@ __global__ __launch_bounds__(kMcBlock) void k_mc10(McArgs a) {
 #pragma unroll
       for (int k = 0; k < 2; k++) {
         if (k >= in.nl) break;
-        const PicDesc& p = in.pic[k];
-        const Plane16 pl{reinterpret_cast<const uint16_t*>(comp == 1 ? p.cb : p.cr), p.cstride, p.width >> 1,
-                         p.height >> 1};
-        pred10<4, 2>(pl, x + in.cix[k], y + in.ciy[k], chroma_taps(in.cfx[k]), 0u, chroma_taps(in.cfy[k]), 0u, uni, o);
+        chroma_pred10(in.pic[k], comp, x + in.cix[k], y + in.ciy[k], in.cfx[k], in.cfy[k], uni, o);
 #pragma unroll
         for (int r = 0; r < 2; r++)
 #pragma unroll

@@ -1,6 +1,7 @@
 // fme_mc_luma.h — xPredInterBlk's building blocks shared by the motion-compensation kernels
-// (fme_mc.hip) and the prediction-error kernel (fme_merge.hip): the interpolation taps, clipMv, the
-// edge-replicated reference window of one output unit and its two-stage filter, at 8 and 10 bits.
+// (fme_mc.hip), the prediction-error kernel (fme_merge.hip) and the skip-check kernel (fme_skip.hip):
+// the luma interpolation taps, clipMv, the edge-replicated reference window of one output unit and
+// its two-stage filter, at 8 and 10 bits.
 // The derivations are in fme_mc.hip's module header.
 #pragma once
 
@@ -14,24 +15,12 @@ namespace mcl {
 
 using namespace simd;
 
-// TComInterpolationFilter.cpp:57-75 as int8 quads (luma: taps 0-3, 4-7; chroma: taps 0-3).
+// TComInterpolationFilter.cpp:57-63 as int8 quads (taps 0-3, 4-7; the chroma taps: fme_mc_chroma.h).
 // Fraction 0 uses the identity filter (64 at the centre tap): through the two-stage form below
 // it reproduces filterCopy and the 1-D filters exactly (fme_mc.hip's module header).
 __device__ __forceinline__ void luma_taps(int f, uint32_t& lo, uint32_t& hi) {
   lo = f == 0 ? q8(0, 0, 0, 64) : f == 1 ? q8(-1, 4, -10, 58) : f == 2 ? q8(-1, 4, -11, 40) : q8(0, 1, -5, 17);
   hi = f == 0 ? 0u : f == 1 ? q8(17, -5, 1, 0) : f == 2 ? q8(40, -11, 4, -1) : q8(58, -10, 4, -1);
-}
-__device__ __forceinline__ uint32_t chroma_taps(int f) {
-  switch (f) {
-    case 0: return q8(0, 64, 0, 0);
-    case 1: return q8(-2, 58, 10, -2);
-    case 2: return q8(-4, 54, 16, -2);
-    case 3: return q8(-6, 46, 28, -4);
-    case 4: return q8(-4, 36, 36, -4);
-    case 5: return q8(-4, 28, 46, -6);
-    case 6: return q8(-2, 16, 54, -4);
-    default: return q8(-2, 10, 58, -2);
-  }
 }
 __device__ __forceinline__ int tap_of(uint32_t lo, uint32_t hi, int k) {   // signed byte k of (lo, hi)
   const uint32_t w = k < 4 ? lo : hi;

@@ -269,6 +269,21 @@ std::vector<fme_merge_res> MergeEstimator::run() {
   return res;
 }
 
+int SkipEstimator::add(const fme_skip_req& req) {
+  reqs_.push_back(req);
+  return (int)reqs_.size() - 1;
+}
+
+std::vector<fme_skip_res> SkipEstimator::run(const fme_skip_params& params) {
+  std::vector<fme_skip_req> reqs;
+  reqs.swap(reqs_);   // the queue is empty afterwards, also when the call throws
+  std::vector<fme_skip_res> res(reqs.size());
+  std::lock_guard<std::mutex> lk(search_.mutex());
+  if (!reqs.empty())
+    check(fme_skip_estimate(search_.ctx(), &params, reqs.data(), res.data(), (int)reqs.size(), nullptr), "fme_skip_estimate");
+  return res;
+}
+
 // ---- InterSearchP -------------------------------------------------------------------------
 
 int InterSearchP::add(const fme_pu_req& req) {

@@ -479,8 +479,9 @@ int fme_integer_search_last_ms(fme_ctx* ctx, float* ms);
  *             step) in m_integerMv2Nx2N[k] (4511-4526), state this context keeps like TEncSearch;
  *   xCheckBestMVP (4344-4394), then the strict-minimum reference choice (3845-3853).
  * The AMVP candidates are the caller's (TComDataCU::fillMvpCand reads CUs the encoder has already
- * decided); bi-prediction (fme_pred_inter_b) and merge estimation (fme_merge.h) are separate entry
- * points, and the mode decision stays with the caller.  The NN state and
+ * decided); bi-prediction (fme_pred_inter_b), merge estimation (fme_merge.h) and the 2Nx2N skip
+ * check (fme_skip.h) are separate entry points; the rest of the mode decision stays with the
+ * caller.  The NN state and
  * m_integerMv2Nx2N follow request order exactly; internally requests are grouped into dependency
  * levels so that each GPU batch holds every request whose inputs are known.                       */
 #define FME_MAX_REFS     4
@@ -564,7 +565,9 @@ int fme_template_costs(fme_ctx* ctx, const fme_pu_req* reqs, uint32_t* costs, in
  *   decision (4041-4105): bi when uiCostBi <= uiCost[0] and <= the best L1 cost over references
  *             not in L0 (costValidList1); else L0 when uiCost[0] <= costValidList1; else L1.
  * Merge estimation and the AMP merge-only test (bTestNormalMC false) follow in fme_merge.h
- * (fme_merge_estimate); getInterMergeCandidates stays with the caller.                          */
+ * (fme_merge_estimate), the skip pass of the 2Nx2N merge RD check in fme_skip.h
+ * (fme_skip_estimate); getInterMergeCandidates and that check's residual pass stay with the
+ * caller.                                                                                       */
 #define FME_PU_FAST_ME_GEN_B 0x02u   /* FastMEForGenBLowDelayEnabled (cfg default true)          */
 #define FME_PU_CLIP_BIPRED   0x04u   /* ClipForBiPredMeEnabled: key clipped to 8 bits            */
 #define FME_PU_MVD_L1_ZERO   0x08u   /* TComSlice::getMvdL1ZeroFlag (GPB slices of lowdelay B,

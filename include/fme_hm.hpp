@@ -34,6 +34,7 @@
 
 #include "fme.h"
 #include "fme_merge.h"
+#include "fme_skip.h"
 
 namespace fme_hm {
 
@@ -172,6 +173,24 @@ class MergeEstimator {
  private:
   FracSearch& search_;
   std::vector<fme_merge_req> reqs_;
+};
+
+// The skip pass (uiNoResidual == 1) of TEncCu::xCheckRDCostMerge2Nx2N (TEncCu.cpp:1157-1282;
+// include/fme_skip.h): per CU and masked-in merge candidate the Y / Cb / Cr motionCompensation, the
+// SSE against the original, the chroma weighting, calcRdCost with the caller's bit count and
+// xCheckBestMode's strict minimum.  The caller queues one fme_skip_req per CU and passes the
+// slice's lambda and chroma distortion weights to run(); the pictures are those of
+// MotionCompensator::setPictureYuv* (the original's chroma planes included).
+class SkipEstimator {
+ public:
+  explicit SkipEstimator(FracSearch& search) : search_(search) {}
+  int add(const fme_skip_req& req);      // index of the request in the pending batch
+  int pending() const { return (int)reqs_.size(); }
+  std::vector<fme_skip_res> run(const fme_skip_params& params);   // the queued requests in order; clears the queue
+
+ private:
+  FracSearch& search_;
+  std::vector<fme_skip_req> reqs_;
 };
 
 // TEncSearch::predInterSearch's uni-directional PU / reference loop for P slices

@@ -14,9 +14,9 @@
  *       xRestrictBipredMergeCand (3665-3679);
  *   the uiMRGCost < uiMECost choice (4126-4171).
  * One kernel launch computes every (PU, motion) distortion of a batch without writing prediction
- * planes.  What stays with the caller: getInterMergeCandidates (it reads decided CUs), the 2Nx2N
- * merge / skip RD check of TEncCu, and weighted prediction (bApplyWeight is false here; the
- * prediction is the unweighted one).                                                            */
+ * planes.  What stays with the caller: getInterMergeCandidates (it reads decided CUs), the
+ * residual pass of TEncCu's 2Nx2N merge RD check (its skip pass is include/fme_skip.h), and
+ * weighted prediction (bApplyWeight is false here; the prediction is the unweighted one).       */
 #ifndef FME_MERGE_H_
 #define FME_MERGE_H_
 
