@@ -467,7 +467,8 @@ __device__ __forceinline__ void store_outputs(fme_result* r, const fme_result* s
   }
 }
 
-// Last-writer scan of NN_pred()'s carried globals (k_nn_tail, k_nn_deep_tail).  Job base + t of
+// Last-writer scan of NN_pred()'s carried globals, a workgroup at a time (k_nn_deep_tail; k_nn_tail
+// uses writer_scan_wave below).  Job base + t of
 // the block's NW waves (t = threadIdx.x) has run[f] = its index when it writes field f (array_e
 // slot f < 8; f = 8: C and the PU size), else -1.  src[f] = the last writer at or before the job
 // (carry[f]: the last writer before `base`, or -1); tot[f] = the block's last writer (or carry).
@@ -497,6 +498,39 @@ __device__ __forceinline__ void writer_scan(const int (&run)[9], const int (&car
     const int prev = pm ? __builtin_amdgcn_readlane(t, 63 - __clzll(pm)) : carry[f];
     src[f] = max(incl[f], prev);
     tot[f] = am ? __builtin_amdgcn_readlane(t, 63 - __clzll(am)) : carry[f];
+  }
+}
+
+// The same scan for a wave on its own (k_nn_tail): no LDS, no barrier, so the waves of a scan
+// block need not run together.  The wave's first job is wbase; the writers of the earlier waves
+// of its scan block are found by reading those jobs again, wave by wave backwards, until every
+// field has one (usually the wave just before: most jobs push all eight slots) or the scan block's
+// start, where carry[f] (k_scatter's blk_prefix) takes over.  `open` and the ballots are
+// wave-uniform.
+__device__ __forceinline__ void writer_scan_wave(const BatchArgs& a, const int (&run)[9], const int32_t* carry,
+                                                 int wbase, int (&src)[9]) {
+  const int lane = (int)threadIdx.x & 63;
+  const unsigned long long below = ~0ull >> (63 - lane);
+  int prev[9];
+  unsigned open = 0x1FFu;   // fields whose last writer before wbase is not known yet
+  for (int pb = wbase - 64; pb >= (wbase & ~(kJobsPerScanBlock - 1)) && open; pb -= 64) {
+    const fme_job pj = load_job(a, pb + lane);   // pb + 63 < wbase < a.n
+    const bool wr = nn_writes_c(pj);
+    const int np = wr ? nn_pushes(pj) : 0;
+#pragma unroll
+    for (int f = 0; f < 9; f++) {
+      const unsigned long long mask = __ballot(f < 8 ? np > f : wr);
+      if ((open >> f & 1u) && mask) {
+        prev[f] = pb + 63 - __clzll(mask);
+        open &= ~(1u << f);
+      }
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < 9; f++) {
+    if (open >> f & 1u) prev[f] = carry[f];
+    const unsigned long long m = __ballot(run[f] >= 0) & below;
+    src[f] = m ? wbase + 63 - __clzll(m) : prev[f];   // a writer in the wave is later than any before it
   }
 }
 

@@ -511,62 +511,52 @@ __device__ __forceinline__ void tail_job(const BatchArgs& a, const WorkBufs& w, 
   store_outputs(r, sr, w.mv_out, i, fx, fy, (uint32_t)(int64_t)val, bits, (uint8_t)cls, status);
 }
 
-// One lane per job; a block scans one 1024-job block (kJobsPerScanBlock, the granularity of
-// k_scatter's carry-in) in rounds of kTailNT jobs, the carry passed from round to round.
-// A/B on the 1080p batch (tools/ab_bench.py, identical results): 1024 lanes at 4 waves/SIMD
-// 0.112 ms, 512 lanes x 2 rounds at 6 waves/SIMD 0.108, 256 x 4 at 6 0.121, at 5 0.119: the tail
-// is bound by its own issue (≈ 3,100 instructions per wave, 1,640 of them packed f32 multiply /
-// add in the reference's k order), not by latency; kept at one round.
-constexpr int kTailNT = kJobsPerScanBlock;
-static_assert(kJobsPerScanBlock % kTailNT == 0, "rounds tile the scan block");
+// One lane per job, one wave per workgroup, every wave on its own: the last-writer scan reads the
+// earlier jobs of the wave's 1024-job scan block (kJobsPerScanBlock, the granularity of k_scatter's
+// carry-in) again instead of meeting the block's other waves at a barrier, so a SIMD takes its next
+// wave whenever one ends.  Until round 8 a workgroup held a whole scan block (one per CU at 4
+// waves/SIMD, 843 of them on 256 CUs, the 16 waves in step through loads, scan, net and stores).
+// A/B on the 1080p batch (tools/ab_bench.py, identical results, profiles/r08_ab.log): that form
+// 0.110 ms; this one 0.091, the same with 128, 256 or 512 lanes per workgroup; at 6 waves/SIMD
+// (73 VGPRs) 0.097.  The net is ≈ 3,100 instructions per wave, 1,640 of them packed f32 multiply /
+// add in the reference's k order.  The packed forms issue in ≈ 4 cycles, plain v_mul_f32 /
+// v_add_f32 in ≈ 2.2 (profiles/r08_valu_rate.txt), so a row pair costs the same either way: the
+// pairs as scalar chains (91 VGPRs) ran 0.113 ms against 0.110 in the scan-block form.
+constexpr int kTailNT = 64;
 
-__global__ __launch_bounds__(kTailNT)
+__global__ __launch_bounds__(kTailNT) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_nn_tail(BatchArgs a, WorkBufs w, const float* __restrict__ nnp_g, int state_in) {
-  __shared__ int32_t wave_tot[kTailNT / 64][9];
-  const int tid = threadIdx.x;
+  const int wbase = (int)blockIdx.x * kTailNT;   // the wave's first job (< a.n by the grid)
+  const int i = wbase + (int)threadIdx.x;
+  const bool valid = i < a.n;
   if (w.sched->invalid) {
-    for (int rnd = 0; rnd < kJobsPerScanBlock / kTailNT; rnd++) {
-      const int i = blockIdx.x * kJobsPerScanBlock + rnd * kTailNT + tid;
-      if (i < a.n) reject_job(a, w, i, state_in);
-    }
+    if (valid) reject_job(a, w, i, state_in);
     return;
   }
-  int carry[9];
-#pragma unroll
-  for (int f = 0; f < 9; f++) carry[f] = w.blk_prefix[blockIdx.x * 9 + f];
-  for (int rnd = 0; rnd < kJobsPerScanBlock / kTailNT; rnd++) {
-    const int base = blockIdx.x * kJobsPerScanBlock + rnd * kTailNT;
-    if (base >= a.n) break;   // block-uniform
-    const int i = base + tid;
-    const bool valid = i < a.n;
-    fme_job j{};
-    // the job and its 64-byte record, issued before the scan's barrier (the NN inputs are
-    // usually the job's own pushes)
-    u32x4 r0{}, r1{}, r2{}, r3{};
-    if (valid) {
-      j = load_job(a, i);
-      const u32x4* rb = reinterpret_cast<const u32x4*>(search_rec(a, w, i));
-      r0 = rb[0];
-      r1 = rb[1];
-      r2 = rb[2];
-      r3 = rb[3];
-    }
-    // writer indices of this job (slots it pushes, C / PU size)
-    int run[9];
-    {
-      const bool wr = valid && nn_writes_c(j);
-      const int np = wr ? nn_pushes(j) : 0;
-#pragma unroll
-      for (int s = 0; s < 8; s++) run[s] = (np > s) ? i : -1;
-      run[8] = wr ? i : -1;
-    }
-    int src[9], tot[9];
-    writer_scan<kTailNT / 64>(run, carry, base, wave_tot, src, tot);
-#pragma unroll
-    for (int f = 0; f < 9; f++) carry[f] = tot[f];
-    if (valid) tail_job(a, w, nnp_g, state_in, i, j, src, r0, r1, r2, r3);
-    if (kJobsPerScanBlock / kTailNT > 1) __syncthreads();   // wave_tot is rewritten next round
+  fme_job j{};
+  // the job and its 64-byte record, issued before the scan (the NN inputs are usually the job's
+  // own pushes)
+  u32x4 r0{}, r1{}, r2{}, r3{};
+  if (valid) {
+    j = load_job(a, i);
+    const u32x4* rb = reinterpret_cast<const u32x4*>(search_rec(a, w, i));
+    r0 = rb[0];
+    r1 = rb[1];
+    r2 = rb[2];
+    r3 = rb[3];
   }
+  // writer indices of this job (slots it pushes, C / PU size)
+  int run[9];
+  {
+    const bool wr = valid && nn_writes_c(j);
+    const int np = wr ? nn_pushes(j) : 0;
+#pragma unroll
+    for (int s = 0; s < 8; s++) run[s] = (np > s) ? i : -1;
+    run[8] = wr ? i : -1;
+  }
+  int src[9];
+  writer_scan_wave(a, run, w.blk_prefix + (wbase / kJobsPerScanBlock) * 9, wbase, src);
+  if (valid) tail_job(a, w, nnp_g, state_in, i, j, src, r0, r1, r2, r3);
 }
 
 
@@ -679,7 +669,7 @@ hipError_t launch_download(const void* src, void* dst, size_t n16, int wgs, hipS
 
 hipError_t launch_nn_tail(const BatchArgs& a, const WorkBufs& w, const float* nn_params,
                           int state_in, hipStream_t s) {
-  const int nb = nblocks(a.n);
+  const int nb = (a.n + kTailNT - 1) / kTailNT;
   hipLaunchKernelGGL(k_nn_tail, dim3(nb), dim3(kTailNT), 0, s, a, w, nn_params, state_in);
   return hipGetLastError();
 }

@@ -64,7 +64,7 @@ def main():
         bat = [t["batch"] for t in times[i]]
         nn = [t["nn_tail"] for t in times[i]]
         print(f"{v:28s} search med {statistics.median(srch):7.3f} min {min(srch):7.3f} ms | "
-              f"nn {statistics.median(nn):6.3f} | batch med {statistics.median(bat):7.3f} ms "
+              f"nn med {statistics.median(nn):6.4f} min {min(nn):6.4f} max {max(nn):6.4f} | batch med {statistics.median(bat):7.3f} ms "
               f"-> {len(jobs) / statistics.median(bat) / 1e3:8.1f} M PU/s | identical={same}")
 
 

@@ -1,5 +1,6 @@
 // Probe: issue rate (independent) and dependent-chain latency of the VALU instructions the search
-// kernel is made of, on gfx950.  Each wave runs ITER x 8 instructions of one kind on 8 independent
+// kernel is made of, and of the NN tail's plain and packed f32 multiply / add, on gfx950
+// (results: profiles/r08_valu_rate.txt).  Each wave runs ITER x 8 instructions of one kind on 8 independent
 // registers (rate) or one chain (latency); printed as SIMD cycles per wave-instruction, derived
 // from wall time at the measured clock: cycles = time * clock * SIMDs / (waves * instructions).
 #include <hip/hip_runtime.h>
@@ -39,7 +40,11 @@
 #define I_LSHLV(r) asm volatile("v_lshlrev_b32 %0, %1, %0" : "+v"(r) : "v"(c));
 #define I_MIN(r) asm volatile("v_min_i32 %0, %0, %1" : "+v"(r) : "v"(b));
 #define I_ADDF(r) asm volatile("v_add_f32 %0, %0, %1" : "+v"(r) : "v"(b));
-#define I_PKFMA(r) asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(r64) : "v"(b64), "v"(c64));
+#define I_MULF(r) asm volatile("v_mul_f32 %0, %0, %1" : "+v"(r) : "v"(b));
+// packed f32: 64-bit register pairs (K64 below)
+#define I_PKFMA(r) asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(r) : "v"(b), "v"(c));
+#define I_PKMULF(r) asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(r) : "v"(b));
+#define I_PKADDF(r) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(r) : "v"(b));
 #define I_XOR(r) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(r) : "v"(b));
 #define I_LSHL(r) asm volatile("v_lshlrev_b32 %0, 3, %0" : "+v"(r));
 #define I_ASHR(r) asm volatile("v_ashrrev_i32 %0, 3, %0" : "+v"(r));
@@ -66,7 +71,28 @@ K(k_mov, I_MOV) K(k_cnd, I_CND) K(k_xor, I_XOR) K(k_lshl, I_LSHL) K(k_ashr, I_AS
 K(k_lshladd, I_LSHLADD) K(k_mad24, I_MAD24) K(k_mullo, I_MULLO) K(k_bfe, I_BFE) K(k_pkmul, I_PKMUL) K(k_udot2, I_UDOT2)
 K(k_fma, I_FMA) K(k_mul24, I_MUL24) K(k_sdwa, I_SDWA) K(k_adddpp, I_ADDDPP) K(k_subrev, I_SUBREV) K(k_pkaddi, I_PKADDI)
 K(k_cvtpk, I_CVTPK) K(k_pack, I_PACK) K(k_cnd64, I_CND64) K(k_cndv, I_CNDV) K(k_and, I_AND) K(k_or, I_OR)
-K(k_lshr, I_LSHR) K(k_lshlv, I_LSHLV) K(k_min, I_MIN) K(k_addf, I_ADDF)
+K(k_lshr, I_LSHR) K(k_lshlv, I_LSHLV) K(k_min, I_MIN) K(k_addf, I_ADDF) K(k_mulf, I_MULF)
+// the NN tail's mix on one accumulator: multiply, then add (8 chains, as the kernel's row chains)
+#define I_MULADDF(r) asm volatile("v_mul_f32 %1, %2, %3\n v_add_f32 %0, %0, %1" : "+v"(r), "=&v"(t) : "v"(b), "v"(c));
+#define I_PKMULADDF(r) asm volatile("v_pk_mul_f32 %1, %2, %3\n v_pk_add_f32 %0, %0, %1" : "+v"(r), "=&v"(t) : "v"(b), "v"(c));
+__global__ void k_muladdf(uint32_t* out, uint32_t s) {
+  uint32_t a0 = s + threadIdx.x, a1 = a0 * 3, a2 = a0 * 5, a3 = a0 * 7, a4 = a0 ^ 9, a5 = a0 + 11, a6 = a0 * 13,
+           a7 = a0 ^ 15, b = s * 17 + threadIdx.x, c = s * 19, t;
+  for (int i = 0; i < ITER / 2; i++) { BODY8(I_MULADDF) }
+  out[blockIdx.x * blockDim.x + threadIdx.x] = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7;
+}
+// 64-bit operands: the packed f32 instructions take register pairs
+#define K64(name, ins, iters)                                                                \
+  __global__ void name(uint32_t* out, uint32_t s) {                                          \
+    uint64_t a0 = s + threadIdx.x, a1 = a0 * 3, a2 = a0 * 5, a3 = a0 * 7, a4 = a0 ^ 9, a5 = a0 + 11, \
+             a6 = a0 * 13, a7 = a0 ^ 15, b = s * 17 + threadIdx.x, c = s * 19, t;             \
+    a0 |= a1 << 32; a2 |= a3 << 32; a4 |= a5 << 32; a6 |= a7 << 32; b |= c << 32; (void)t;    \
+    for (int i = 0; i < iters; i++) { BODY8(ins) }                                          \
+    const uint64_t x = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7;                                 \
+    out[blockIdx.x * blockDim.x + threadIdx.x] = (uint32_t)x ^ (uint32_t)(x >> 32);           \
+  }
+K64(k_pkfma, I_PKFMA, ITER) K64(k_pkmulf, I_PKMULF, ITER) K64(k_pkaddf, I_PKADDF, ITER)
+K64(k_pkmuladdf, I_PKMULADDF, ITER / 2)
 // dependent chain: one register
 #define KD(name, ins)                                                                        \
   __global__ void name(uint32_t* out, uint32_t s) {                                          \
@@ -93,6 +119,8 @@ int main() {
     {"add_u32_sdwa", k_sdwa}, {"add_u32_dpp", k_adddpp}, {"sub_u32", k_subrev}, {"pk_add_i16", k_pkaddi},
     {"cvt_pk_i16_i32", k_cvtpk}, {"pack_b32_f16", k_pack}, {"cndmask_e64(s)", k_cnd64}, {"cmp+cndmask(vcc)", k_cndv},
     {"and_b32", k_and}, {"or_b32", k_or}, {"lshrrev", k_lshr}, {"lshlrev(v)", k_lshlv}, {"min_i32", k_min}, {"add_f32", k_addf},
+    {"mul_f32", k_mulf}, {"pk_fma_f32", k_pkfma}, {"pk_mul_f32", k_pkmulf}, {"pk_add_f32", k_pkaddf},
+    {"mul+add_f32", k_muladdf}, {"pk_mul+pk_add_f32", k_pkmuladdf},
     {"DEP dot4c", d_dot4c}, {"DEP dot2c", d_dot2c}, {"DEP pk_sub", d_pksub}, {"DEP perm", d_perm}, {"DEP add", d_add},
     {"DEP alignbyte", d_align}};
   hipEvent_t e0, e1;
