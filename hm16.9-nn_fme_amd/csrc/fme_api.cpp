@@ -82,7 +82,6 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
     const size_t nb = (n + kJobsPerScanBlock - 1) / kJobsPerScanBlock;
     HIP_TRY(c->cls.reserve(n));
     HIP_TRY(c->perm.reserve(n));
-    if (FME_SJOBS) HIP_TRY(c->sjobs.reserve(n));
     HIP_TRY(c->blk_agg.reserve(nb * 9));
     HIP_TRY(c->blk_prefix.reserve(nb * 9));
   }
@@ -147,7 +146,7 @@ int fme_destroy(fme_ctx* c) {
   for (auto& e : c->ev_sse)
     if (e) (void)hipEventDestroy(e);
   c->d_pics.release(); c->d_mlambda.release(); c->d_keys.release(); c->d_nn.release(); c->d_net.release();
-  c->d_jobs.release(); c->d_res.release(); c->d_mv.release(); c->koff.release(); c->cls.release(); c->perm.release(); c->sjobs.release();
+  c->d_jobs.release(); c->d_res.release(); c->d_mv.release(); c->koff.release(); c->cls.release(); c->perm.release();
   c->counts.release(); c->blk_agg.release(); c->blk_prefix.release(); c->nn_state.release();
   c->d_sched.release();
   if (c->ev_done) (void)hipEventDestroy(c->ev_done);
@@ -434,7 +433,6 @@ static int ensure_work(fme_ctx* c, int n) {
   const size_t nb = ((size_t)n + kJobsPerScanBlock - 1) / kJobsPerScanBlock;
   HIP_TRY(c->cls.reserve(n));
   HIP_TRY(c->perm.reserve(n));
-  if (FME_SJOBS) HIP_TRY(c->sjobs.reserve(n));
   HIP_TRY(c->blk_agg.reserve(nb * 9));
   HIP_TRY(c->blk_prefix.reserve(nb * 9));
   HIP_TRY(c->koff.reserve(n));
@@ -459,7 +457,6 @@ static WorkBufs work_bufs(fme_ctx* c) {
   WorkBufs w{};
   w.cls = c->cls.p;
   w.perm = c->perm.p;
-  w.sjobs = c->sjobs.p;
   w.koff = c->koff.p;
   w.counts = c->counts.p + c->counts_cur * kCountWords;
   w.counts_next = c->counts.p + (c->counts_cur ^ 1) * kCountWords;
@@ -966,7 +963,6 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   HIP_TRY(launch_scatter(a, w, c->sched_p, s));   // with its own class offsets (the schedule goes unused)
   TzArgs ta{};
   ta.a = a;
-  ta.sjobs = c->sjobs.p;
   ta.perm = c->perm.p;
   ta.jobs_out = d_jobs;
   ta.ext = d_ext;

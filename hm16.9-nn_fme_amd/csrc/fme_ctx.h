@@ -125,7 +125,6 @@ struct fme_ctx {
   fme::DevBuf<int32_t> koff;         // packed batches: key offset per keyed job (k_classify)
   fme::DevBuf<uint8_t> cls;
   fme::DevBuf<int32_t> perm;
-  fme::DevBuf<fme_job> sjobs;
   fme::DevBuf<int32_t> counts;      // two counter blocks (kCountWords each), used by alternate batches
   int counts_cur = 0;          // the block the next batch counts in (zero unless counts_dirty)
   bool counts_dirty = false;   // the blocks are not known to be zero: the next batch fills both

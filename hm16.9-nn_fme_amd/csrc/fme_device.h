@@ -10,25 +10,10 @@
 #include "../../include/fme_skip.h"
 #include "fme_srv_pack.h"
 
-// 0 (default): k_scatter writes only the permutation and the searches gather jobs[perm[i]];
-// 1: k_scatter also copies each job into class order (sjobs) for contiguous reads.  Same search
-// time on the 1080p frame (0.901 against 0.896 ms, profiles/r05_ab.log) for 27.6 MB less written
-// and read per batch.  A build variant for that A/B, not a second path.
-#ifndef FME_SJOBS
-#define FME_SJOBS 0
-#endif
 // 1: the bulk integer search stages each (kernel, reference, CTU) group's search area in LDS
 // (fme_tz.hip k_tz_staged); 0: one wave per PU straight from the class order (k_tz_wave)
 #ifndef FME_TZ_STAGE
 #define FME_TZ_STAGE 1
-#endif
-// Sub-bands per XCD queue of the search kernel (Schedule::xq): the XCD searches its spatial band
-// of the frame in this many consecutive strips, every class of a strip before the next strip, so
-// the jobs' lines and the reference windows a strip's PU classes share stay in the XCD's L2.
-// 1 = the round-4 order (each XCD's band class by class), the default: 8 strips cut the search's
-// fetch by 7 % and cost 6 % of its time (0.955 against 0.899 ms; 16: 0.969 ms, profiles/r05_ab.log).
-#ifndef FME_LANE_SUBBANDS
-#define FME_LANE_SUBBANDS 1
 #endif
 
 namespace fme {
@@ -178,8 +163,6 @@ struct Schedule;
 struct WorkBufs {
   uint8_t* cls;          // [n] class id, 255 = invalid
   int32_t* perm;         // [n] jobs grouped by class (original index)
-  fme_job* sjobs;        // [n] copies of the jobs in class order (FME_SJOBS 1: the searches read
-                         // them contiguously; 0: they read jobs[perm[i]] and k_scatter writes none)
   int32_t* koff;         // [n] BatchArgs::koff as k_classify writes it (packed batches)
   int32_t* counts;       // [kNumClasses + 1]: per-class count, [24] = invalid jobs
   int32_t* counts_next;  // the other counter block: k_scatter zeroes it for the next batch
@@ -195,18 +178,16 @@ struct WorkBufs {
 __device__ __forceinline__ const fme_result* search_rec(const BatchArgs& a, const WorkBufs&, int i) { return a.res + i; }
 
 // Schedule of the search kernel (k_scatter builds it on the device): class c's jobs are
-// sjobs/perm[class_off[c] .. + class_cnt[c]) and its 64-lane wave tiles [prefix[c], prefix[c+1]).
+// perm[class_off[c] .. + class_cnt[c]) and its 64-lane wave tiles [prefix[c], prefix[c+1]).
 struct Schedule {
   int32_t prefix[kNumClasses + 1];
   int32_t class_off[kNumClasses];
   int32_t class_cnt[kNumClasses];
-  // The lane kernel's per-XCD tile queues.  Every class's wave tiles are split into 8 S
-  // contiguous bands (S = FME_LANE_SUBBANDS; band B holds tiles [nt B / 8S, nt (B+1) / 8S) of a
-  // class with nt tiles), XCD x owns bands x S .. x S + S - 1, and its queue lists them band by
-  // band, class by class inside a band in the order lane_class_at: xq[x][s][i] = the queue's tiles
-  // before (band x S + s, class lane_class_at(i)); xq[x][s][kNumClasses] = before band s + 1
-  // (xq[x][S-1][kNumClasses] = its length).
-  int32_t xq[8][FME_LANE_SUBBANDS][kNumClasses + 1];
+  // The lane kernel's per-XCD tile queues.  Every class's wave tiles are split into 8 contiguous
+  // bands (band x holds tiles [nt x / 8, nt (x+1) / 8) of a class with nt tiles), XCD x owns band x,
+  // and its queue lists the band class by class in the order lane_class_at: xq[x][i] = the queue's
+  // tiles before class lane_class_at(i); xq[x][kNumClasses] = its length.
+  int32_t xq[8][kNumClasses + 1];
   int32_t invalid;            // jobs rejected by k_classify (the whole batch is then skipped)
   int32_t pad_[3];
 };
@@ -218,10 +199,9 @@ struct SchedParams {
 };
 SchedParams sched_params();
 
-// One integer-search launch (fme_tz.hip): the batch, its class-ordered copy and the outputs.
+// One integer-search launch (fme_tz.hip): the batch, its class order and the outputs.
 struct TzArgs {
   BatchArgs a;
-  const fme_job* sjobs;
   const int32_t* perm;
   fme_job* jobs_out;          // mv_x / mv_y written per job
   const fme_tz_ext* ext;
@@ -311,6 +291,7 @@ struct NnIn11 {   // NN_pred() inputs of a single call: array_e slots[8], C, PUH
 hipError_t launch_server(SrvBox* box, const float* nn, uint32_t served, uint32_t epoch, uint64_t idle_ticks,
                          uint64_t life_ticks, int bit_depth, hipStream_t s);
 int lane_lanes_per_pu(int cls);                    // lanes of a class's PU group (pow2), 0: none
+int lane_grid(int n, int reserve);                 // workgroups of a lane-kernel launch of n jobs (fme_lane.hip)
 int cu_count(int device);                          // compute units (workgroup budget of a launch)
 // Packed NN layout for the tail kernel (nn_pack, fme_kernels.hip): offsets in floats, every
 // pair region 8-byte aligned.

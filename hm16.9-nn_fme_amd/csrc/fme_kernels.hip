@@ -12,7 +12,7 @@
 //              the search's tile ranges and per-XCD queues), jobs grouped by class
 //              (block-aggregated atomics), and the other counter block zeroed for the next batch,
 //              which therefore needs no fill dispatch.
-//   search     EMI square step + FracDIF per tile of same-shape PUs (fme_search.hip).
+//   search     EMI square step + FracDIF per tile of same-shape PUs (fme_lane.hip, fme_lane10.hip).
 //   nn_tail    prefix-max over jobs resolves which earlier job last wrote each array_e slot
 //              (the reference's stale global state, TEncSearch.cpp:55-57, 198-201), then
 //              NN_pred() (85-204) and the xMotionEstimation tail (4586-4597), one lane per job.
@@ -26,29 +26,13 @@
 #include <algorithm>
 
 #include "fme_device.h"
+#include "fme_simd.h"
 
 namespace fme {
 
 // ---------------------------------------------------------------------------------------
 // small helpers
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ int clamp_i(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// TComRdCost::xGetExpGolombNumberOfBits (TComRdCost.cpp:172-185) in closed form.
-__device__ __forceinline__ uint32_t eg_bits(int v) {
-  const uint32_t t = v <= 0 ? ((uint32_t)(-v) << 1) + 1u : ((uint32_t)v << 1);
-  return 1u + 2u * (31u - (uint32_t)__clz((int)t));
-}
-
-__device__ __forceinline__ uint32_t mv_bits(int x, int y, int scale, int px, int py) {
-  return eg_bits((x << scale) - px) + eg_bits((y << scale) - py);
-}
-
-// TComRdCost::getCost (TComRdCost.h:165): (Distortion)((lambda * b) / 65536.0).
-__device__ __forceinline__ uint32_t mv_cost(double ml, uint32_t bits) {
-  return (uint32_t)((ml * (double)bits) / 65536.0);
-}
-
 // HEVC luma taps (TComInterpolationFilter.cpp:57-63), selected without memory traffic.
 __device__ __forceinline__ void luma_taps(int f, int (&c)[8]) {
   if (f == 1) {
@@ -238,21 +222,14 @@ __device__ __forceinline__ int build_schedule(const int32_t* __restrict__ counts
     const int ex = wave_excl_scan(nb);
     if (c <= kNumClasses) sc->prefix[c] = ex;     // [kNumClasses] = the total
   }
-  // per-XCD queues of bands (Schedule::xq): band B of class c = its tiles [nb B / 8S, nb (B+1) / 8S)
-  constexpr int S = FME_LANE_SUBBANDS;
-  auto band_lo = [&](int B) { return (int)(((long long)nb * B) / (8 * S)); };
+  // per-XCD queues (Schedule::xq): band x of class c = its tiles [nb x / 8, nb (x+1) / 8)
+  auto band_lo = [&](int B) { return (int)(((long long)nb * B) / 8); };
 #pragma unroll 1
   for (int x = 0; x < 8; x++) {
-    int run = 0;
-#pragma unroll 1
-    for (int q = 0; q < S; q++) {
-      const int B = x * S + q;
-      const int mine_c = c < kNumClasses ? band_lo(B + 1) - band_lo(B) : 0;   // class c's band tiles
-      const int mine = __shfl(mine_c, c < kNumClasses ? lane_class_at(c) : c);  // position c's
-      const int ex = run + wave_excl_scan(mine);
-      if (c <= kNumClasses) sc->xq[x][q][c] = ex;
-      run = __shfl(ex, kNumClasses);
-    }
+    const int mine_c = c < kNumClasses ? band_lo(x + 1) - band_lo(x) : 0;   // class c's band tiles
+    const int mine = __shfl(mine_c, c < kNumClasses ? lane_class_at(c) : c);  // position c's
+    const int ex = wave_excl_scan(mine);
+    if (c <= kNumClasses) sc->xq[x][c] = ex;
   }
   if (c == 0) sc->invalid = inv;
   return off;
@@ -264,15 +241,11 @@ __global__ __launch_bounds__(kBlock) void k_scatter(BatchArgs a, WorkBufs w, Sch
   const int base = blockIdx.x * kJobsPerScanBlock;
   int rank[kJobsPerScanBlock / kBlock];
   int cls[kJobsPerScanBlock / kBlock];
-  fme_job jb[kJobsPerScanBlock / kBlock];   // loaded up front, beside the class bytes
 #pragma unroll
   for (int q = 0; q < kJobsPerScanBlock / kBlock; q++) {
     const int i = base + q * kBlock + tid;
     cls[q] = 255;
-    if (i < a.n) {
-      cls[q] = w.cls[i];
-      if (FME_SJOBS) jb[q] = load_job(a, i);
-    }
+    if (i < a.n) cls[q] = w.cls[i];
   }
   if (tid < 64) {
     const int off = build_schedule(w.counts, sp, w.sched, blockIdx.x == 0);
@@ -292,11 +265,7 @@ __global__ __launch_bounds__(kBlock) void k_scatter(BatchArgs a, WorkBufs w, Sch
 #pragma unroll
   for (int q = 0; q < kJobsPerScanBlock / kBlock; q++) {
     const int i = base + q * kBlock + tid;
-    if (cls[q] < kNumClasses) {
-      const int dst = class_off[cls[q]] + basep[cls[q]] + rank[q];
-      w.perm[dst] = i;
-      if (FME_SJOBS) w.sjobs[dst] = jb[q];
-    }
+    if (cls[q] < kNumClasses) w.perm[class_off[cls[q]] + basep[cls[q]] + rank[q]] = i;
   }
   // Exclusive prefix-max of the NN-writer aggregates over the blocks before this one: k_nn_tail's
   // carry-in of the stale-state scan.  It depends on k_classify only, so it is computed here,
@@ -503,10 +472,10 @@ __device__ __forceinline__ void tail_job(const BatchArgs& a, const WorkBufs& w, 
     offy = 2 * hy + qy;
   }
   const int fx = 4 * mvx + offx, fy = 4 * mvy + offy;
-  const uint32_t mvb = mv_bits(fx, fy, 0, j.mvp_x, j.mvp_y);
+  const uint32_t mvb = simd::mv_bits(fx, fy, 0, j.mvp_x, j.mvp_y);
   const uint32_t bits = (uint32_t)j.bits_in + mvb;
   const double fw = (j.flags & FME_JOB_BIPRED) ? 0.5 : 1.0;
-  const double val = floor(fw * ((double)frac_cost - (double)mv_cost(ml, mvb))) + (double)mv_cost(ml, bits);
+  const double val = floor(fw * ((double)frac_cost - (double)simd::mv_cost(ml, mvb))) + (double)simd::mv_cost(ml, bits);
   // gcc/x86-64 (Distortion)(double) semantics for the cost
   store_outputs(r, sr, w.mv_out, i, fx, fy, (uint32_t)(int64_t)val, bits, (uint8_t)cls, status);
 }

@@ -26,53 +26,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <type_traits>
-#include <utility>
 
-#include "fme_device.h"
-#include "fme_simd.h"
+#include "fme_lane_common.h"
 
-#ifndef FME_XCD_SWIZZLE
-#define FME_XCD_SWIZZLE 1
-#endif
-// Candidates per quarter pass (2: column-phase pairs, 1: one candidate per pass — fewer live
-// registers, the first-stage column recomputed per candidate) and half-stage vertical pairs
-// {(0,-1),(0,1)} and {(s,-1),(s,1)} in one pass (2) or one candidate per pass (1); the 8x4 unit
-// shape always uses 1 (lane_unit).  A/B on the 1080p batch (tools/ab_bench.py, one kernel for
-// every class, all shapes alike): 1/1 1.185 ms, QPAIR 2 1.146, HPAIR 2 1.091, both 2 1.054 — the
-// shared first stages save more issue slots than the extra live key - pred array costs at
-// 2 waves/SIMD (FME_LANE_WAVES 3 spills: 1.480 ms).
-#ifndef FME_LANE_QPAIR
-#define FME_LANE_QPAIR 1
-#endif
-#ifndef FME_LANE_HPAIR
-#define FME_LANE_HPAIR 2
-#endif
-#ifndef FME_LANE_PAIR84   // 1: the 8x4 unit shape paired too
-#define FME_LANE_PAIR84 0
-#endif
 // Each PU class's search is its own function (noinline): inlined into one switch, the classes'
 // hoisted constants and live ranges merged into one allocation that spilled (1,286 VGPRs and
-// 2,098 SGPRs at 3 waves/SIMD) although every class alone fits.
-#ifndef FME_LANE_UNIT_ATTR
-#define FME_LANE_UNIT_ATTR __attribute__((noinline))
-#endif
-// 1: the half stage's six side candidates from shared half columns and the quarter stage as three
-// column-phase passes of all their candidates (fewest first stages; needs 2 waves/SIMD of
-// registers); 0: the pair modes above
-#ifndef FME_LANE_SHARE
-#define FME_LANE_SHARE 1
-#endif
-// 1: the 2-D passes' second stage with taps scaled by 16, so a pair of outputs is packed by one
-// v_perm of the two sums' high halves ((16 s) >> 16 == s >> 12) and clipped as a packed pair
-// (v_pk_max_i16 / v_pk_min_i16), and the 1-D horizontal rows of the half stage shifted and clipped
-// as the packed pairs the vertical pass already holds: 3 instructions per output pair instead of 5
-// (two shifts, two med3, one perm).  0: per-output shift and clamp.  A/B on the 1080p batch
-// (tools/ab_bench.py, identical results): search 0.904 -> 0.871 ms, batch 1.087 -> 1.055 ms
-// (profiles/r06_ab.log).
-#ifndef FME_LANE_PK16
-#define FME_LANE_PK16 1
-#endif
+// 2,098 SGPRs at 3 waves/SIMD) although every class alone fits.  (The build options whose A/Bs
+// are settled are listed in DESIGN.md §4.)
+
 // occupancy target (waves per SIMD) that bounds the register allocation
 #ifndef FME_LANE_WAVES
 #define FME_LANE_WAVES 2
@@ -94,10 +55,6 @@ namespace fme {
 __device__ unsigned long long g_lane_stamps[kNumClasses][8];
 #endif
 namespace {
-using namespace simd;
-
-#define FME_AI __attribute__((always_inline))
-
 #if FME_LANE_STAMPS
 __device__ __forceinline__ unsigned long long lane_stamp() {
   unsigned long long t;
@@ -110,39 +67,6 @@ __device__ __forceinline__ unsigned long long lane_stamp() {
 #else
 #define FME_STAMP(k) (void)0
 #endif
-
-constexpr int kLaneNT = 256;
-
-// ---- small helpers -------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
-}
-// Sum over the L lanes of a PU's group (L a power of two <= 64): every lane of the group ends
-// with the total.  Offsets 1, 2 swap within a quad (DPP quad_perm); once each quad / octet
-// holds its sum, the half-mirror / mirror partner of a lane (DPP row_half_mirror / row_mirror,
-// lane i <-> 7-i / 15-i) lies in the other quad / octet; 16 is a ds_swizzle xor, 32 a
-// bpermute.  (A/B on the 1080p batch: -1 % search time against bpermute for every step.)
-template <int L>
-__device__ __forceinline__ uint32_t group_sum(uint32_t v) {
-  if (L >= 2) v += dpp<0xB1>(v);
-  if (L >= 4) v += dpp<0x4E>(v);
-  if (L >= 8) v += dpp<0x141>(v);
-  if (L >= 16) v += dpp<0x140>(v);
-  if (L >= 32) v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);
-  if (L >= 64) v += (uint32_t)__shfl_xor((int)v, 32, 64);
-  return v;
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-__host__ __device__ __forceinline__ constexpr int pow2_at_least(int v) { return v <= 1 ? 1 : 2 * pow2_at_least((v + 1) / 2); }
 
 // The first dot product of a chain with an inline-constant accumulator, in the VOP3P encoding:
 // the compiler picks v_dot4c / v_dot2c (accumulator tied to the destination) and materialises the
@@ -158,8 +82,6 @@ __device__ __forceinline__ int dot2_k0(uint32_t a, uint32_t b) {
   return d;
 }
 
-// low 16 bits of a and b -> one packed pair (a in the low half)
-__device__ __forceinline__ uint32_t pack2(int a, int b) { return __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x05040100u); }
 __device__ __forceinline__ int clamp_s8(int v) { return min(max(v, -128), 127); }
 
 // Bytes (b, b+1) of two dwords (row r0 in src1, row r1 in src0) -> sign-extended int16 pair.
@@ -167,16 +89,6 @@ __device__ __forceinline__ uint32_t sext_pair(uint32_t hi_row, uint32_t lo_row, 
   const uint32_t sel = (uint32_t)byte | 0x0c00u | ((uint32_t)(4 + byte) << 16) | 0x0c000000u;
   const uint32_t z = __builtin_amdgcn_perm(hi_row, lo_row, sel);    // zero-extended s' bytes
   return pk_sub(z ^ 0x00800080u, 0x00800080u);                       // sign extension
-}
-
-// Opaque to the optimiser (no instructions): values derived from the window before this point
-// are not reused after it, so common subexpressions do not stay live across passes.
-template <int R, int N>
-__device__ __forceinline__ void launder(uint32_t (&v)[R][N]) {
-#pragma unroll
-  for (int r = 0; r < R; r++)
-#pragma unroll
-    for (int k = 0; k < N; k++) asm volatile("" : "+v"(v[r][k]));
 }
 
 // 4 bytes starting at byte b of a row held in dwords v[0..N).  Every caller passes a b that
@@ -221,20 +133,18 @@ __device__ __forceinline__ int tap(int f, int k) {
 }
 // Coefficient pairs for a vertical 8-tap filter of fraction f whose taps start `o` rows into
 // a span of 10 rows read as 5 packed row pairs: pair t = (tap(2t - o), tap(2t + 1 - o)), scaled by
-// kVS (FME_LANE_PK16: 16).
-constexpr int kVS = FME_LANE_PK16 ? 16 : 1;
+// kVS = 16: a pair of second-stage outputs is then packed by one v_perm of the two sums' high
+// halves ((16 s) >> 16 == s >> 12) and clipped as a packed pair (v_pk_max_i16 / v_pk_min_i16),
+// 3 instructions per output pair instead of 5 (two shifts, two med3, one perm).
+constexpr int kVS = 16;
 __device__ __forceinline__ void vpairs(int f, int o, uint32_t (&c)[5]) {
 #pragma unroll
   for (int t = 0; t < 5; t++) c[t] = p16(kVS * tap(f, 2 * t - o), kVS * tap(f, 2 * t + 1 - o));
 }
 // (s0 >> 12, s1 >> 12) clipped to the s - 128 range, packed, from second-stage sums scaled by kVS.
 __device__ __forceinline__ uint32_t pk_round2d(int s0, int s1) {
-  if constexpr (FME_LANE_PK16) {
-    const v2s m = up(__builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, 0x07060302u));   // high halves
-    return pk(__builtin_elementwise_min(__builtin_elementwise_max(m, v2s{-128, -128}), v2s{127, 127}));
-  } else {
-    return pack2(clamp_s8(s0 >> 12), clamp_s8(s1 >> 12));
-  }
+  const v2s m = up(__builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, 0x07060302u));   // high halves
+  return pk(__builtin_elementwise_min(__builtin_elementwise_max(m, v2s{-128, -128}), v2s{127, 127}));
 }
 // (h0 >> 6, h1 >> 6) clipped, from the packed pair (h0, h1) of 1-D sums (+32 carried)
 __device__ __forceinline__ uint32_t pk_round1d(uint32_t hp) {
@@ -345,50 +255,12 @@ __device__ __forceinline__ uint32_t unit_dist(uint32_t (&X)[UW][UH / 2], const M
   }
 }
 
-// Candidate offsets (xPatternRefinement tables, TEncSearch.cpp:212-236).
-__host__ __device__ __forceinline__ constexpr int h9_dx(int i) { return (i == 3 || i == 5 || i == 7) ? -1 : ((i == 4 || i == 6 || i == 8) ? 1 : 0); }
-__host__ __device__ __forceinline__ constexpr int h9_dy(int i) { return (i == 1 || i == 5 || i == 6) ? -1 : ((i == 2 || i == 7 || i == 8) ? 1 : 0); }
-__host__ __device__ __forceinline__ constexpr int q9_dx(int i) { return (i == 3 || i == 5 || i == 7) ? -1 : ((i == 4 || i == 6 || i == 8) ? 1 : 0); }
-__host__ __device__ __forceinline__ constexpr int q9_dy(int i) { return (i == 1 || i == 3 || i == 4) ? -1 : ((i == 2 || i == 7 || i == 8) ? 1 : 0); }
-// Q9 index of (dqx, dqy)
-__host__ __device__ __forceinline__ constexpr int q9_index(int dx, int dy) {
-  return dy == 0 ? (dx == 0 ? 0 : (dx < 0 ? 5 : 6)) : dy < 0 ? (dx == 0 ? 1 : (dx < 0 ? 3 : 4)) : (dx == 0 ? 2 : (dx < 0 ? 7 : 8));
-}
-// EMI positions: 0 centre, then TL, T, TR, L, R, BL, B, BR (xTZ8PointSquareSearch order)
-__host__ __device__ __forceinline__ constexpr int emi_dx(int p) { return (p == 1 || p == 4 || p == 6) ? -1 : ((p == 3 || p == 5 || p == 8) ? 1 : 0); }
-__host__ __device__ __forceinline__ constexpr int emi_dy(int p) { return p >= 1 && p <= 3 ? -1 : (p >= 6 ? 1 : 0); }
-
 // =============================================================================================
 // Candidate passes of one unit.  v: re-centred window (rows -4..UH+3, cols -4..UW+3, s - 128
 // bytes), K: key - 128 as packed column pairs.  Each pass keeps at most two key - pred arrays.
 // =============================================================================================
-// `live`: ~0 on the lanes of a PU's units, 0 on the idle lanes that pad a group of 6 / 12 / 48
-// units (AMP shapes) to a power of two, so they add nothing to the group's sum.
-// The MV cost from the workgroup's table: g_cost[lambda][bits] = (UInt)(mlambda * bits / 65536.0)
-// (TComRdCost.h:165), computed once per launch by the same double arithmetic.
-__device__ __forceinline__ uint32_t mv_cost(const uint32_t* ml, uint32_t bits) { return ml[bits]; }
-template <int L>
-__device__ __forceinline__ void take_half(int i, uint32_t part, uint32_t live, const uint32_t* ml, int mvx, int mvy, int px,
-                                          int py, uint32_t& best, int& bi) {
-  const uint32_t d = group_sum<L>(part & live) + mv_cost(ml, mv_bits(2 * mvx + h9_dx(i), 2 * mvy + h9_dy(i), 1, px, py));
-  if (d < best || (d == best && i < bi)) {
-    best = d;
-    bi = i;
-  }
-}
-template <int L>
-__device__ __forceinline__ void take_qtr(int i, uint32_t part, uint32_t live, const uint32_t* ml, int mvx, int mvy, int hx,
-                                         int hy, int px, int py, uint32_t& best, int& bi) {
-  const int qx = 2 * hx + q9_dx(i), qy = 2 * hy + q9_dy(i);
-  const uint32_t d = group_sum<L>(part & live) + mv_cost(ml, mv_bits(4 * mvx + qx, 4 * mvy + qy, 0, px, py));
-  if (d < best || (d == best && i < bi)) {
-    best = d;
-    bi = i;
-  }
-}
-
 // (0,0), (0,-1), (0,1)
-template <int UW, int UH, int T, int HPM>
+template <int UW, int UH, int T>
 __device__ __forceinline__ void half_center(uint32_t (&v)[UH + 8][UW / 4 + 2], const KeySrc<UW, UH / 2>& K,
                                             const Metric& had, uint32_t (&d)[3]) {
   constexpr int RV = UH + 8, UJ = UH / 2;
@@ -404,9 +276,8 @@ __device__ __forceinline__ void half_center(uint32_t (&v)[UH + 8][UW / 4 + 2], c
     d[0] = unit_dist<UW, UH, T>(X, had);
   }
   launder(v);
-  // (0,-1), (0,1): vertical half-pel on integer columns (transposed window')
-  auto vpass = [&](auto sel_c) FME_AI {   // sel 1: (0,-1) only, 2: (0,1) only, 3: both
-    constexpr int sel = decltype(sel_c)::value;
+  // (0,-1), (0,1): vertical half-pel on integer columns (transposed window'), both in one pass
+  {
     uint32_t X1[UW][UJ], X2[UW][UJ];
 #pragma unroll
     for (int g = 0; g < UW / 4; g++) {
@@ -424,98 +295,20 @@ __device__ __forceinline__ void half_center(uint32_t (&v)[UH + 8][UW / 4 + 2], c
         const int x = 4 * g + c4;
         int v1[UH + 1];   // half rows i = 0..UH (between rows i-1, i): taps on window' rows i..i+7
 #pragma unroll
-        for (int i = (sel == 2 ? 1 : 0); i <= (sel == 1 ? UH - 1 : UH); i++) {
+        for (int i = 0; i <= UH; i++) {
           const int acc = dot4(rbytes(CB[c4], i), c2lo, 32);
           v1[i] = clamp_s8(dot4(rbytes(CB[c4], i + 4), c2hi, acc) >> 6);
         }
 #pragma unroll
         for (int jj = 0; jj < UJ; jj++) {
-          if (sel & 1) X1[x][jj] = pk_sub(K.at(x, jj), pack2(v1[2 * jj], v1[2 * jj + 1]));
-          if (sel & 2) X2[x][jj] = pk_sub(K.at(x, jj), pack2(v1[2 * jj + 1], v1[2 * jj + 2]));
+          X1[x][jj] = pk_sub(K.at(x, jj), pack2(v1[2 * jj], v1[2 * jj + 1]));
+          X2[x][jj] = pk_sub(K.at(x, jj), pack2(v1[2 * jj + 1], v1[2 * jj + 2]));
         }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if (sel & 1) d[1] = unit_dist<UW, UH, T>(X1, had);
-    if (sel & 2) d[2] = unit_dist<UW, UH, T>(X2, had);
-  };
-  if constexpr (HPM == 2) {
-    vpass(std::integral_constant<int, 3>{});
-  } else {
-    vpass(std::integral_constant<int, 1>{});
-    launder(v);
-    vpass(std::integral_constant<int, 2>{});
-  }
-}
-
-// (s,0), (s,-1), (s,1) for s = -1 (SIDE 0: half column x) or +1 (SIDE 1: half column x+1)
-template <int UW, int UH, int T, int SIDE, int HPM>
-__device__ __forceinline__ void half_side(uint32_t (&v)[UH + 8][UW / 4 + 2], const KeySrc<UW, UH / 2>& K,
-                                          const Metric& had, uint32_t (&d)[3]) {
-  constexpr int RV = UH + 8, UJ = UH / 2;
-  uint32_t c2lo, c2hi;
-  taps8(2, c2lo, c2hi);
-  launder(v);
-  {   // (s,0): horizontal half-pel, half column jc = x + SIDE (window' bytes jc .. jc+7)
-    uint32_t X[UW][UJ];
-#pragma unroll
-    for (int x = 0; x < UW; x++) {
-      const int jc = x + SIDE;
-      int h1[UH];
-#pragma unroll
-      for (int y = 0; y < UH; y++)
-        h1[y] = clamp_s8(dot4(rbytes(v[y + 4], jc + 4), c2hi, dot4(rbytes(v[y + 4], jc), c2lo, 32)) >> 6);
-#pragma unroll
-      for (int jj = 0; jj < UJ; jj++) X[x][jj] = pk_sub(K.at(x, jj), pack2(h1[2 * jj], h1[2 * jj + 1]));
-    }
-    d[0] = unit_dist<UW, UH, T>(X, had);
-  }
-  launder(v);
-  // (s,-1), (s,1): 2-D half-pel (first stage rows -4..UH+3 of half column jc, then vertical)
-  auto dpass = [&](auto sel_c) FME_AI {   // sel 1: (s,-1) only, 2: (s,1) only, 3: both
-    constexpr int sel = decltype(sel_c)::value;
-    const uint32_t c16[4] = {p16(-1, 4), p16(-11, 40), p16(40, -11), p16(4, -1)};
-    const uint32_t c16o[5] = {p16(0, -1), p16(4, -11), p16(40, 40), p16(-11, 4), p16(-1, 0)};
-    uint32_t XB[UW][UJ], XC[UW][UJ];
-#pragma unroll
-    for (int x = 0; x < UW; x++) {
-      const int jc = x + SIDE;
-      launder(v);
-      uint32_t HP[RV / 2];
-#pragma unroll
-      for (int r = 0; r < RV; r += 2) {
-        const int h0 = dot4(rbytes(v[r], jc + 4), c2hi, dot4(rbytes(v[r], jc), c2lo, 0));
-        const int h1 = dot4(rbytes(v[r + 1], jc + 4), c2hi, dot4(rbytes(v[r + 1], jc), c2lo, 0));
-        HP[r / 2] = pack2(h0, h1);
-      }
-      int v2[UH + 1];
-#pragma unroll
-      for (int i = (sel == 2 ? 1 : 0); i <= (sel == 1 ? UH - 1 : UH); i++) {
-        int acc = 2048;
-        if ((i & 1) == 0) {
-#pragma unroll
-          for (int t = 0; t < 4; t++) acc = dot2(HP[i / 2 + t], c16[t], acc);
-        } else {
-#pragma unroll
-          for (int t = 0; t < 5; t++) acc = dot2(HP[(i - 1) / 2 + t], c16o[t], acc);
-        }
-        v2[i] = clamp_s8(acc >> 12);
-      }
-#pragma unroll
-      for (int jj = 0; jj < UJ; jj++) {
-        if (sel & 1) XB[x][jj] = pk_sub(K.at(x, jj), pack2(v2[2 * jj], v2[2 * jj + 1]));
-        if (sel & 2) XC[x][jj] = pk_sub(K.at(x, jj), pack2(v2[2 * jj + 1], v2[2 * jj + 2]));
-      }
-      __builtin_amdgcn_sched_barrier(0);   // one column at a time (register pressure)
-    }
-    if (sel & 1) d[1] = unit_dist<UW, UH, T>(XB, had);
-    if (sel & 2) d[2] = unit_dist<UW, UH, T>(XC, had);
-  };
-  if constexpr (HPM == 2) {
-    dpass(std::integral_constant<int, 3>{});
-  } else {
-    dpass(std::integral_constant<int, 1>{});
-    dpass(std::integral_constant<int, 2>{});
+    d[1] = unit_dist<UW, UH, T>(X1, had);
+    d[2] = unit_dist<UW, UH, T>(X2, had);
   }
 }
 
@@ -546,7 +339,7 @@ __device__ __forceinline__ void half_sides(uint32_t (&v)[UH + 8][UW / 4 + 2], co
 #pragma unroll
     for (int r = 0; r < RV; r += 2) HP[r / 2] = pack2(hv[r], hv[r + 1]);
     uint32_t X0[UJ], XM[UJ], XP[UJ];   // (s,0), (s,-1), (s,1) of this column
-    int v2[UH + 1];   // second-stage sums (FME_LANE_PK16: x 16), rounded below
+    int v2[UH + 1];   // second-stage sums (x kVS), rounded below
 #pragma unroll
     for (int i = 0; i <= UH; i++) {   // half rows between window rows i+3, i+4
       int acc;
@@ -560,19 +353,14 @@ __device__ __forceinline__ void half_sides(uint32_t (&v)[UH + 8][UW / 4 + 2], co
 #pragma unroll
         for (int t = 2; t < 5; t++) acc = dot2(HP[(i - 1) / 2 + t], c16o[t], acc);
       }
-      v2[i] = FME_LANE_PK16 ? acc : clamp_s8(acc >> 12);
+      v2[i] = acc;
     }
+    // the 1-D horizontal rows are shifted and clipped as the packed pairs the vertical pass holds
 #pragma unroll
     for (int jj = 0; jj < UJ; jj++) {
-      if constexpr (FME_LANE_PK16) {
-        X0[jj] = pk_round1d(HP[2 + jj]);   // rows 4 + 2 jj, 5 + 2 jj of the first stage
-        XM[jj] = pk_round2d(v2[2 * jj], v2[2 * jj + 1]);
-        XP[jj] = pk_round2d(v2[2 * jj + 1], v2[2 * jj + 2]);
-      } else {
-        X0[jj] = pack2(clamp_s8(hv[4 + 2 * jj] >> 6), clamp_s8(hv[5 + 2 * jj] >> 6));
-        XM[jj] = pack2(v2[2 * jj], v2[2 * jj + 1]);
-        XP[jj] = pack2(v2[2 * jj + 1], v2[2 * jj + 2]);
-      }
+      X0[jj] = pk_round1d(HP[2 + jj]);   // rows 4 + 2 jj, 5 + 2 jj of the first stage
+      XM[jj] = pk_round2d(v2[2 * jj], v2[2 * jj + 1]);
+      XP[jj] = pk_round2d(v2[2 * jj + 1], v2[2 * jj + 2]);
     }
 #pragma unroll
     for (int jj = 0; jj < UJ; jj++) {
@@ -648,109 +436,6 @@ __device__ __forceinline__ void qtr_col(uint32_t (&v)[UH + 8][UW / 4 + 2], const
   for (int m = 0; m < NP; m++) d[m] = unit_dist<UW, UH, T>(XQ[m], had);
 }
 
-// Quarter passes: pass PS covers column phase k = QP_K[PS] (dqx = k-1) and one or two row
-// phases l (dqy = l-1); candidate (k1, l1) is the half best.  A phase with fraction 0 filters
-// with {0,0,0,64,0,0,0,0}, which equals HM's copy / 1-D paths after rounding.
-// QM 2: five passes, (k, l) = (0: 0,1) (0: 2) (1: 0,2) (2: 0,1) (2: 2); QM 1: eight, (k, l) for
-// k, l in 0..2 without (1,1).
-template <int QM> __host__ __device__ __forceinline__ constexpr int qp_passes() { return QM == 2 ? 5 : 8; }
-template <int QM> __host__ __device__ __forceinline__ constexpr int qp_k(int ps) {
-  return QM == 2 ? (ps < 2 ? 0 : (ps == 2 ? 1 : 2)) : (ps + (ps >= 4 ? 1 : 0)) / 3;
-}
-template <int QM> __host__ __device__ __forceinline__ constexpr int qp_l0(int ps) {
-  return QM == 2 ? ((ps == 1 || ps == 4) ? 2 : 0) : (ps + (ps >= 4 ? 1 : 0)) % 3;
-}
-template <int QM> __host__ __device__ __forceinline__ constexpr int qp_l1(int ps) {
-  return QM == 2 ? (ps == 0 ? 1 : (ps == 2 ? 2 : (ps == 3 ? 1 : -1))) : -1;
-}
-// Q9 index of pass ps's first / second candidate
-template <int QM> __host__ __device__ __forceinline__ constexpr int qp_idx0(int ps) {
-  return q9_index(qp_k<QM>(ps) - 1, qp_l0<QM>(ps) - 1);
-}
-template <int QM> __host__ __device__ __forceinline__ constexpr int qp_idx1(int ps) {
-  return qp_l1<QM>(ps) < 0 ? -1 : q9_index(qp_k<QM>(ps) - 1, qp_l1<QM>(ps) - 1);
-}
-
-template <int UW, int UH, int T, int QM, int PS>
-__device__ __forceinline__ void qtr_pass(uint32_t (&v)[UH + 8][UW / 4 + 2], const KeySrc<UW, UH / 2>& K,
-                                         const Metric& had, int hx, int hy, uint32_t (&d)[2]) {
-  constexpr int RV = UH + 8, UJ = UH / 2;
-  constexpr int k = qp_k<QM>(PS);
-  constexpr int NP = qp_l1<QM>(PS) < 0 ? 1 : 2;
-  const int LS[2] = {qp_l0<QM>(PS), qp_l1<QM>(PS) < 0 ? 0 : qp_l1<QM>(PS)};
-  const int qx = 2 * hx + (k - 1);
-  const int ix = qx >> 2, fx = qx & 3;
-  const uint32_t dlt = (uint32_t)(1 + ix);
-  uint32_t clo, chi;
-  taps8_any(fx, clo, chi);
-  uint32_t cpe[NP][5], cpo[NP][5];
-#pragma unroll
-  for (int m = 0; m < NP; m++) {
-    const int qy = 2 * hy + (LS[m] - 1);
-    const int iy = qy >> 2, fy = qy & 3;
-    vpairs(fy, 1 + iy, cpe[m]);
-    vpairs(fy, 2 + iy, cpo[m]);
-  }
-  uint32_t XQ[NP][UW][UJ];
-#pragma unroll
-  for (int x = 0; x < UW; x++) {
-    launder(v);
-    uint32_t HQ[RV / 2];
-#pragma unroll
-    for (int r = 0; r < RV; r += 2) {
-      const int h0 = dot4(rbytes_d(v[r], x + 4, dlt), chi, dot4(rbytes_d(v[r], x, dlt), clo, 0));
-      const int h1 = dot4(rbytes_d(v[r + 1], x + 4, dlt), chi, dot4(rbytes_d(v[r + 1], x, dlt), clo, 0));
-      HQ[r / 2] = pack2(h0, h1);
-    }
-#pragma unroll
-    for (int m = 0; m < NP; m++) {
-      int vq[UH];
-#pragma unroll
-      for (int y = 0; y < UH; y++) {
-        const int m0 = (y & 1) ? (y - 1) / 2 : y / 2;
-        int acc = 2048 * kVS;
-#pragma unroll
-        for (int t = 0; t < 5; t++) acc = dot2(HQ[m0 + t], (y & 1) ? cpo[m][t] : cpe[m][t], acc);
-        vq[y] = acc;
-      }
-#pragma unroll
-      for (int jj = 0; jj < UJ; jj++) XQ[m][x][jj] = pk_sub(K.at(x, jj), pk_round2d(vq[2 * jj], vq[2 * jj + 1]));
-    }
-    __builtin_amdgcn_sched_barrier(0);   // one column at a time (register pressure)
-  }
-  d[0] = unit_dist<UW, UH, T>(XQ[0], had);
-  d[1] = NP > 1 ? unit_dist<UW, UH, T>(XQ[NP - 1], had) : 0u;
-}
-
-typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t u32x3a __attribute__((ext_vector_type(3), aligned(4)));
-typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
-typedef __attribute__((address_space(1))) const u32x4a gu4;
-typedef __attribute__((address_space(1))) const u32x3a gu3;
-typedef __attribute__((address_space(1))) const u32x2a gu2;
-
-// N dwords from byte address p, any alignment (gfx950 runs global memory in unaligned access
-// mode; tools/probes/unaligned_probe.hip checks it on the box).
-template <int N>
-__device__ __forceinline__ void ld_bytes(const void* p, uint32_t (&o)[N]) {
-  const uint8_t* q = (const uint8_t*)p;
-  constexpr int K4 = N / 4 * 4;
-#pragma unroll
-  for (int k = 0; k < K4; k += 4) {
-    const u32x4a v = *(gu4*)(q + 4 * k);
-    o[k] = v.x; o[k + 1] = v.y; o[k + 2] = v.z; o[k + 3] = v.w;
-  }
-  if constexpr (N - K4 == 3) {
-    const u32x3a v = *(gu3*)(q + 4 * K4);
-    o[K4] = v.x; o[K4 + 1] = v.y; o[K4 + 2] = v.z;
-  } else if constexpr (N - K4 == 2) {
-    const u32x2a v = *(gu2*)(q + 4 * K4);
-    o[K4] = v.x; o[K4 + 1] = v.y;
-  } else if constexpr (N - K4 == 1) {
-    o[K4] = gld32(q + 4 * K4);
-  }
-}
-
 // Rows y0 .. y0+R-1, 4N bytes from column x0 of a picture, as (sample - 128) bytes, with HM's
 // padded-picture semantics (TComPicYuv::extendPicBorder): rows and columns clamped to the
 // picture.  Away from the left / right edges each row is one unaligned load; near them each dword
@@ -798,31 +483,6 @@ __device__ __forceinline__ void load_window(const PicDesc& pic, int x0, int y0, 
     for (int k = 0; k < N; k++) v[r][k] ^= 0x80808080u;
 }
 
-// Per-workgroup copies of the batch's picture and lambda tables (k_search_lane fills them once):
-// every tile reads its PU's reference / original picture descriptor and motion lambda from LDS
-// instead of a dependent global load before its window loads.
-__shared__ PicDesc g_pics[FME_MAX_PICTURES];
-// MV bits of one candidate: two exp-Golomb lengths of values below 2^18 (int16 MVs and predictors,
-// cost scale <= 2), each at most 37.
-constexpr int kCostBits = 80;
-__shared__ uint32_t g_cost[FME_MAX_LAMBDAS][kCostBits];
-// Record staging: each PU's 64-byte fme_result is assembled in LDS by the PU's first lane, then
-// the wave writes the tile's records with four lanes per record, so every store instruction writes
-// whole 64-byte lines (one lane per record wrote four separate 16-byte pieces: 256 bytes of
-// WRITE_SIZE per job).
-__shared__ uint4 g_rec[256 / 64][64][4];
-__shared__ int32_t g_rec_jid[256 / 64][64];
-
-
-// Global pointers typed as such (global_load / global_store, not flat).
-typedef __attribute__((address_space(1))) const fme_job g_job;
-typedef __attribute__((address_space(1))) const int32_t g_i32;
-typedef __attribute__((address_space(1))) fme_result g_res;
-typedef __attribute__((address_space(1))) const int16_t g_i16;
-typedef __attribute__((address_space(1))) const uint8_t g_u8;
-typedef __attribute__((address_space(1))) const uint32_t g_u32;
-
-
 // =============================================================================================
 // One lane: unit (ux, uy) of PU p of class (PW x PH), unit UW x UH (4x8, or 8x4 for the shapes
 // whose height is not a multiple of 8).  PUs of more than 64 units (48x64, 64x48, 64x64) give a
@@ -835,10 +495,8 @@ template <int PW, int PH, int UW, int UH>
 // it saved and restored 114 callee-saved VGPRs per call.)
 // (The lane comes from mbcnt and the wave index is an argument: a callee that reads no work-item
 // id needs none passed, so the caller keeps no VGPR of it alive, and reloads none, around the call.)
-__device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* __restrict__ sjobs_,
-                                             const int32_t* __restrict__ perm_, int cls_off, int cls_cnt,
-                                             int wt, int wid) {
-  g_job* const sjobs = (g_job*)sjobs_;
+__device__ __attribute__((noinline)) void lane_unit(const BatchArgs& a, const int32_t* __restrict__ perm_, int cls_off,
+                                                    int cls_cnt, int wt, int wid) {
   g_i32* const perm = (g_i32*)perm_;
   g_res* const outp = (g_res*)a.res;
   g_i16* const keys = (g_i16*)a.keys;
@@ -846,8 +504,6 @@ __device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* 
   constexpr int T = ((PW % 8) == 0 && (PH % 8) == 0) ? 8 : 4;
   static_assert((T == 8 && UW == 4 && UH == 8) || (T == 4 && UW == 4 && UH == 4) || (T == 4 && UW * UH == 32),
                 "4x8 units (a lane pair per 8x8 SATD tile) or 4x4 units (one 4x4 tile per lane)");
-  constexpr bool k84 = UW == 8 && UH == 4 && !FME_LANE_PAIR84;
-  constexpr int kQP = k84 ? 1 : FME_LANE_QPAIR, kHP = k84 ? 1 : FME_LANE_HPAIR;
   static_assert(PW % UW == 0 && PH % UH == 0, "units tile the PU");
   constexpr int UX = PW / UW, UY = PH / UH, NU = UX * UY;
   constexpr int UPL = NU > 64 ? 2 : 1;                // units per lane
@@ -865,28 +521,17 @@ __device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* 
   constexpr int EW = (UW + 2 + 3) / 4;        // EMI window dwords per row (cols -1 .. UW)
   constexpr int KW = UW / 2;                  // key dwords per row (bytes: UW / 4 used; int16 pairs: UW / 2)
 
-  const int lane = (int)__lane_id();
-  const int gl = wt * 64 + lane;               // wave tile wt: 64 lanes = 64 / L PUs
-  int p = gl / L;
-  const int u = gl - p * L;
-  const bool active = p < cls_cnt;
-  if (!active) p = cls_cnt - 1;              // duplicate work, no stores (keeps the group whole)
-  const uint32_t live = u < NUH ? ~0u : 0u;  // padding lanes repeat the last unit, summed as 0
-  const int uu = u < NUH ? u : NUH - 1;
-  const int ux = uu % UX, uy = uu / UX;
+  const LaneMap lm = lane_map<L, NUH, UX>(wt, cls_cnt);
+  const int lane = lm.lane, ux = lm.ux, uy = lm.uy;
+  const uint32_t live = lm.live;
 
   FME_STAMP(0);
-  const int jid = perm[cls_off + p];
+  const int jid = perm[cls_off + lm.p];
+  // The caller's job by its index: a packed row expanded, or the fme_job.  (Keep "declared, then
+  // assigned": initialised from the call, every class's register assignment shifts, +0.13 %
+  // instructions and 4 B more scratch)
   fme_job j;
-  if (FME_SJOBS) {   // two 16-byte global loads (a struct copy through an address-space-1 pointer does
-                     // not compile in the host pass): the class-ordered copy
-    g_job* const src = sjobs + cls_off + p;
-    const u32x4a q0 = *(gu4*)src, q1 = *(gu4*)((g_u8*)src + 16);
-    uint32_t tmp[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-    __builtin_memcpy(&j, tmp, sizeof(j));
-  } else {           // the caller's job by its index: a packed row expanded, or the fme_job
-    j = load_job(a, jid);
-  }
+  j = load_job(a, jid);
   // The reference's descriptor is read from LDS where a window is loaded (an opaque index keeps
   // the compiler from holding the 40-byte copy in registers, or scratch, across the passes).
   auto ref_pic = [&]() FME_AI -> PicDesc {
@@ -1058,6 +703,8 @@ __device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* 
     mvy = by;
   }
   FME_STAMP(2);
+  const int u = lm.u;
+  const bool active = lm.active;
   typedef __attribute__((address_space(1))) u32x4a gw4;
   if (u == 0) {   // bytes 16..63 of the record: cost, bits (NN tail), c, emi[8], n_emi
     g_rec[wid][lane][1] = make_uint4(0u, 0u, cval, emi[0]);
@@ -1065,7 +712,6 @@ __device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* 
     g_rec[wid][lane][3] = make_uint4(emi[5], emi[6], emi[7], (uint32_t)n_emi);
     g_rec_jid[wid][lane] = !active ? -1 : jid;   // destination record (call order)
   }
-
 
   // ---- the resident half: window rows -4..UH+3, cols -4..UW+3 around mv_int', and the key as
   // signed int16 (key - 128) pairs K[c][j] = (row 2j, row 2j+1) of column c ----------------------
@@ -1112,36 +758,24 @@ __device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* 
   };
 
   // ---- 2. half-pel stage (H9 order: (0,0),(0,-1),(0,1),(-1,0),(1,0),(-1,-1),(1,-1),(-1,1),(1,1)) ---
-  // Candidates arrive out of H9 order: keep the first strict minimum in H9 order with an index
-  // tie-break (d < best, or d == best at a lower index).
   uint32_t hbest = 0xFFFFFFFFu;
   int hbi = 9;
   {
     uint32_t d[3] = {0u, 0u, 0u};
-    over_halves([&](uint32_t (&dd)[3]) FME_AI { half_center<UW, UH, T, kHP>(v, K, met, dd); }, d);
-    take_half<L>(0, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(1, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(2, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    over_halves([&](uint32_t (&dd)[3]) FME_AI { half_center<UW, UH, T>(v, K, met, dd); }, d);
+    take_half<L, 0>(0, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, 0>(1, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, 0>(2, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
   }
-  if constexpr (FME_LANE_SHARE) {
+  {
     uint32_t d[6];
     over_halves([&](uint32_t (&dd)[6]) FME_AI { half_sides<UW, UH, T>(v, K, met, dd); }, d);
-    take_half<L>(3, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(5, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(7, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(4, d[3], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(6, d[4], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(8, d[5], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-  } else {
-    uint32_t d[3];
-    over_halves([&](uint32_t (&dd)[3]) FME_AI { half_side<UW, UH, T, 0, kHP>(v, K, met, dd); }, d);
-    take_half<L>(3, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(5, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(7, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    over_halves([&](uint32_t (&dd)[3]) FME_AI { half_side<UW, UH, T, 1, kHP>(v, K, met, dd); }, d);
-    take_half<L>(4, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(6, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(8, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, 0>(3, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, 0>(5, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, 0>(7, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, 0>(4, d[3], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, 0>(6, d[4], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, 0>(8, d[5], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
   }
   const int hx = h9_dx(hbi), hy = h9_dy(hbi);
   FME_STAMP(4);
@@ -1149,27 +783,15 @@ __device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* 
   // ---- 3. quarter-pel stage: passes over column phases (Q9 candidate 0 = the half best) -------
   uint32_t qbest = hbest;
   int qbi = 0;
-  auto qone = [&](auto ps_c) FME_AI {
-    constexpr int ps = decltype(ps_c)::value;
-    uint32_t d[2];
-    over_halves([&](uint32_t (&dd)[2]) FME_AI { qtr_pass<UW, UH, T, kQP, ps>(v, K, met, hx, hy, dd); }, d);
-    take_qtr<L>(qp_idx0<kQP>(ps), d[0], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
-    if constexpr (qp_l1<kQP>(ps) >= 0)
-      take_qtr<L>(qp_idx1<kQP>(ps), d[1], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
+  auto qcol = [&](auto k_c) FME_AI {
+    constexpr int kk = decltype(k_c)::value;
+    uint32_t d[3];
+    over_halves([&](uint32_t (&dd)[3]) FME_AI { qtr_col<UW, UH, T, kk>(v, K, met, hx, hy, dd); }, d);
+    take_qtr<L, 0>(q9_index(kk - 1, -1), d[0], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
+    take_qtr<L, 0>(q9_index(kk - 1, kk == 1 ? 1 : 0), d[1], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
+    if constexpr (kk != 1) take_qtr<L, 0>(q9_index(kk - 1, 1), d[2], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
   };
-  if constexpr (FME_LANE_SHARE) {
-    auto qcol = [&](auto k_c) FME_AI {
-      constexpr int kk = decltype(k_c)::value;
-      uint32_t d[3];
-      over_halves([&](uint32_t (&dd)[3]) FME_AI { qtr_col<UW, UH, T, kk>(v, K, met, hx, hy, dd); }, d);
-      take_qtr<L>(q9_index(kk - 1, -1), d[0], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
-      take_qtr<L>(q9_index(kk - 1, kk == 1 ? 1 : 0), d[1], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
-      if constexpr (kk != 1) take_qtr<L>(q9_index(kk - 1, 1), d[2], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
-    };
-    static_for<0, 3>(qcol);
-  } else {
-    static_for<0, qp_passes<kQP>()>(qone);
-  }
+  static_for<0, 3>(qcol);
   const int bq = qbi;
   FME_STAMP(5);
 
@@ -1197,6 +819,7 @@ __device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* 
       }
     }
   }
+
 #if FME_LANE_STAMPS
   FME_STAMP(6);
   if (lane == 0) {   // vector atomics into the debug buffer, one lane per wave
@@ -1217,119 +840,21 @@ __device__ FME_LANE_UNIT_ATTR void lane_unit(const BatchArgs& a, const fme_job* 
 #endif
 }
 
-// The XCD this wave runs on (HW_REG_XCC_ID, gfx940+: bits 3:0).
-__device__ __forceinline__ int xcc_id() {
-#if FME_XCD_SWIZZLE
-  return __builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11)) & 7;
-#else
-  return 0;
-#endif
-}
-
 }  // namespace
 
-// (class id, PU W, PU H, unit W, unit H) — fme_device.h class table; one kernel per unit
-// shape, since a kernel's register allocation is the maximum over its cases.
-// 4x8 units for every shape whose width is a multiple of 4 and height a multiple of 8 (an 8x8
-// SATD tile is a lane pair; the 4x4-tiled 4x8 / 4x16 / 12x16 keep their two tiles in the lane),
-// 4x4 units (one SATD tile each) for 8x4 / 16x4 / 16x12.  (4x4 units for 4x8-tiled shapes: about
-// 18 % more instructions per PU, measured 0.924 -> 0.9xx ms; 8x4 units for the 8x4-like shapes gave
-// wrong half / quarter results on ~15 % of their golden jobs and are not used)
-#ifndef FME_LANE_4X8_UNITS44   // 4x8 PUs as two 4x4 units (a lane pair) instead of one lane each
-#define FME_LANE_4X8_UNITS44 0
-#endif
-#if FME_LANE_4X8_UNITS44
-#define FME_LANE48_CLASSES(X) X(3, 4, 16, 4, 8)
-#define FME_LANE84_CLASSES(X) X(0, 4, 8, 4, 4) X(1, 8, 4, 4, 4) X(4, 16, 4, 4, 4)
-#else
-#define FME_LANE48_CLASSES(X) X(0, 4, 8, 4, 8) X(3, 4, 16, 4, 8)
-#define FME_LANE84_CLASSES(X) X(1, 8, 4, 4, 4) X(4, 16, 4, 4, 4)
-#endif
-#define FME_LANE88_CLASSES(X)                                                                        \
-  X(2, 8, 8, 4, 8) X(5, 8, 16, 4, 8) X(6, 16, 8, 4, 8) X(9, 16, 16, 4, 8) X(10, 8, 32, 4, 8)         \
-  X(11, 32, 8, 4, 8) X(12, 16, 32, 4, 8) X(13, 32, 16, 4, 8) X(16, 32, 32, 4, 8) X(17, 16, 64, 4, 8) \
-  X(18, 64, 16, 4, 8) X(19, 32, 64, 4, 8) X(20, 64, 32, 4, 8) X(23, 64, 64, 4, 8)
-// the AMP shapes whose unit count is not a power of two: 12x16 (6 of 8 lanes), 16x12 in 4x4 units
-// (12 of 16), 24x32 / 32x24 (24 of 32), 48x64 / 64x48 (two halves of 48 units, 48 of 64 lanes)
-#define FME_LANE_AMP_CLASSES(X)                                                                      \
-  X(7, 12, 16, 4, 8) X(8, 16, 12, 4, 4) X(14, 24, 32, 4, 8) X(15, 32, 24, 4, 8) X(21, 48, 64, 4, 8)   \
-  X(22, 64, 48, 4, 8)
-#ifndef FME_LANE_CLASSES   // (a subset may be given on the command line for register-usage probes)
-#define FME_LANE_CLASSES(X) \
-  FME_LANE48_CLASSES(X) FME_LANE84_CLASSES(X) FME_LANE88_CLASSES(X) FME_LANE_AMP_CLASSES(X)
-#endif
-
-// One kernel serves every lane class.  A workgroup claims four consecutive 64-lane wave tiles
-// (one per wave; a tile holds 64 / L PUs of one class) per atomic from its XCD's queue
-// (Schedule::xq: the XCD's contiguous eighth of every class's tiles = one spatial band of the
-// CTU-ordered job stream, so each L2 sees one band, searched strip by strip with every class of a
-// strip together, and the four waves of a CU search neighbouring PUs whose reference windows share
-// L1 lines), then from the other XCDs' queues.  The next claim is issued before the current tiles
-// are searched.  The grid is sized to fill the chip, not to the (device-computed) tile count, so
-// the host never waits for the class histogram.
-// Measured (1080p frame, tools/ab_bench.py): per-wave claims 1.48 ms, four tiles per workgroup
-// 1.21 ms, eight 1.24, sixteen 1.29; without the XCD queues 1.25 (the per-wave claim form was
-// kept as a build option until round 5 and removed unused).
+// One kernel serves every class (FME_LANE_CLASSES; lane_claim_loop, fme_lane_common.h).
 #define FME_CASE(ID, PW_, PH_, UW_, UH_)                                                             \
   case ID:                                                                                           \
-    lane_unit<PW_, PH_, UW_, UH_>(a, w.sjobs, w.perm, sc->class_off[ID], sc->class_cnt[ID], wt, wid); \
+    lane_unit<PW_, PH_, UW_, UH_>(a, w.perm, sc->class_off[ID], sc->class_cnt[ID], wt, wid);         \
     break;
 __global__ __launch_bounds__(kLaneNT) __attribute__((amdgpu_waves_per_eu(FME_LANE_WAVES)))
 void k_search_lane(BatchArgs a, WorkBufs w) {
-  constexpr int S = FME_LANE_SUBBANDS;
-  const Schedule* __restrict__ sc = w.sched;
-  int32_t* ctr = w.tile_ctr;
-  __shared__ int32_t s_xq[8][S][kNumClasses + 1];
-  {   // the batch's tables and the XCD queues, once per workgroup
-    const uint32_t* ps = reinterpret_cast<const uint32_t*>(a.pics);
-    uint32_t* pd = reinterpret_cast<uint32_t*>(g_pics);
-    for (int i = threadIdx.x; i < (int)(sizeof(g_pics) / 4); i += kLaneNT) pd[i] = ps[i];
-    for (int i = threadIdx.x; i < FME_MAX_LAMBDAS * kCostBits; i += kLaneNT)
-      g_cost[i / kCostBits][i % kCostBits] = simd::mv_cost(a.mlambda[i / kCostBits], (uint32_t)(i % kCostBits));
-    for (int i = threadIdx.x; i < 8 * S * (kNumClasses + 1); i += kLaneNT) (&s_xq[0][0][0])[i] = (&sc->xq[0][0][0])[i];
-  }
-  const int home = xcc_id(), wid = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  constexpr int kGroup = kLaneNT / 64;   // wave tiles per claim
-  __shared__ int32_t claim[2];
-  int x = home, tried = 0, par = 0;
-  if (threadIdx.x == 0) claim[0] = atomicAdd(&ctr[x], 1);
-  __syncthreads();
-  int t = __builtin_amdgcn_readfirstlane(claim[0]);
-  while (true) {
-    const int len = s_xq[x][S - 1][kNumClasses];
-    if (kGroup * t >= len) {   // queue drained: the next XCD's
-      if (++tried == 8) break;
-      x = (home + tried) & 7;
-      par ^= 1;
-      if (threadIdx.x == 0) claim[par] = atomicAdd(&ctr[x], 1);
-      __syncthreads();
-      t = __builtin_amdgcn_readfirstlane(claim[par]);
-      continue;
+  lane_claim_loop<kLaneNT>(a, w, [&](const Schedule* sc, int c, int wt, int wid) FME_AI {
+    switch (c) {
+      FME_LANE_CLASSES(FME_CASE)
+      default: break;
     }
-    int nxt = 0;
-    if (threadIdx.x == 0) nxt = atomicAdd(&ctr[x], 1);
-    const int tw = kGroup * t + wid;
-    if (tw < len) {
-      int q = 0, c = 0;   // band x S + q of the queue, class c inside it
-      while (q < S - 1 && tw >= s_xq[x][q][kNumClasses]) q++;
-      while (c < kNumClasses - 1 && tw >= s_xq[x][q][c + 1]) c++;
-      const int ci = c;   // queue position -> class
-      c = lane_class_at(ci);
-      const int nt = sc->prefix[c + 1] - sc->prefix[c];
-      const int lo = (int)(((long long)nt * (x * S + q)) / (8 * S));   // the band's first tile of class c
-      // wave-uniform: kept in an SGPR, so no VGPR of it lives (and is spilled) across the call
-      const int wt = __builtin_amdgcn_readfirstlane(lo + (tw - s_xq[x][q][ci]));
-      switch (c) {
-        FME_LANE_CLASSES(FME_CASE)
-        default: break;
-      }
-    }
-    par ^= 1;   // claim[par] is rewritten only after every wave has passed the barrier below
-    if (threadIdx.x == 0) claim[par] = nxt;
-    __syncthreads();
-    t = __builtin_amdgcn_readfirstlane(claim[par]);
-  }
-  (void)wid;
+  });
 }
 #undef FME_CASE
 
@@ -1347,7 +872,7 @@ int lane_lanes_per_pu(int cls) {
 // Workgroups of the lane-kernel launch: at most the wave tiles n jobs could need (4 per
 // workgroup), at most 4 per CU (the kernel holds 2; spare workgroups find the queues drained
 // and exit).
-static int lane_grid(int n, int reserve) {
+int lane_grid(int n, int reserve) {
   static int cus = 0;
   if (!cus) {
     int dev = 0;

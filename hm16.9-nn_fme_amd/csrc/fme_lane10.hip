@@ -23,58 +23,17 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <type_traits>
-#include <utility>
 
-#include "fme_device.h"
-#include "fme_simd.h"
+#include "fme_lane_common.h"
 
 namespace fme {
 namespace {
-using namespace simd;
-
-#define FME_AI __attribute__((always_inline))
-
 #ifndef FME_L10_WAVES   // occupancy target (waves per SIMD) that bounds the register allocation
 #define FME_L10_WAVES 2
 #endif
 
-constexpr int kL10NT = 256;
 constexpr int kDsh = 2;      // DISTORTION_PRECISION_ADJUSTMENT(bitDepth - 8)
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
-}
-// Sum over the L lanes of a PU's group (every lane of the group ends with the total).
-template <int L>
-__device__ __forceinline__ uint32_t group_sum(uint32_t v) {
-  if (L >= 2) v += dpp<0xB1>(v);
-  if (L >= 4) v += dpp<0x4E>(v);
-  if (L >= 8) v += dpp<0x141>(v);
-  if (L >= 16) v += dpp<0x140>(v);
-  if (L >= 32) v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);
-  if (L >= 64) v += (uint32_t)__shfl_xor((int)v, 32, 64);
-  return v;
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-__host__ __device__ __forceinline__ constexpr int pow2_at_least(int v) { return v <= 1 ? 1 : 2 * pow2_at_least((v + 1) / 2); }
-
-template <int R, int N>
-__device__ __forceinline__ void launder(uint32_t (&v)[R][N]) {
-#pragma unroll
-  for (int r = 0; r < R; r++)
-#pragma unroll
-    for (int k = 0; k < N; k++) asm volatile("" : "+v"(v[r][k]));
-}
-
-__device__ __forceinline__ uint32_t pack2(int a, int b) { return __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x05040100u); }
 __device__ __forceinline__ int sx16(uint32_t v) { return (int)(int16_t)(v & 0xffffu); }
 __device__ __forceinline__ int hx16(uint32_t v) { return (int)v >> 16; }
 
@@ -232,72 +191,7 @@ __device__ __forceinline__ uint32_t unit_dist(uint32_t (&X)[UW][UH / 2], const M
   }
 }
 
-// Candidate tables (xPatternRefinement, TEncSearch.cpp:212-236)
-__host__ __device__ __forceinline__ constexpr int h9_dx(int i) { return (i == 3 || i == 5 || i == 7) ? -1 : ((i == 4 || i == 6 || i == 8) ? 1 : 0); }
-__host__ __device__ __forceinline__ constexpr int h9_dy(int i) { return (i == 1 || i == 5 || i == 6) ? -1 : ((i == 2 || i == 7 || i == 8) ? 1 : 0); }
-__host__ __device__ __forceinline__ constexpr int q9_dx(int i) { return (i == 3 || i == 5 || i == 7) ? -1 : ((i == 4 || i == 6 || i == 8) ? 1 : 0); }
-__host__ __device__ __forceinline__ constexpr int q9_dy(int i) { return (i == 1 || i == 3 || i == 4) ? -1 : ((i == 2 || i == 7 || i == 8) ? 1 : 0); }
-__host__ __device__ __forceinline__ constexpr int q9_index(int dx, int dy) {
-  return dy == 0 ? (dx == 0 ? 0 : (dx < 0 ? 5 : 6)) : dy < 0 ? (dx == 0 ? 1 : (dx < 0 ? 3 : 4)) : (dx == 0 ? 2 : (dx < 0 ? 7 : 8));
-}
-__host__ __device__ __forceinline__ constexpr int emi_dx(int p) { return (p == 1 || p == 4 || p == 6) ? -1 : ((p == 3 || p == 5 || p == 8) ? 1 : 0); }
-__host__ __device__ __forceinline__ constexpr int emi_dy(int p) { return p >= 1 && p <= 3 ? -1 : (p >= 6 ? 1 : 0); }
-
-__shared__ PicDesc g10_pics[FME_MAX_PICTURES];
-constexpr int kCostBits = 80;
-__shared__ uint32_t g10_cost[FME_MAX_LAMBDAS][kCostBits];
-__shared__ uint4 g10_rec[kL10NT / 64][64][4];
-__shared__ int32_t g10_rec_jid[kL10NT / 64][64];
-
-__device__ __forceinline__ uint32_t mvc(const uint32_t* ml, uint32_t bits) { return ml[bits]; }
-template <int L>
-__device__ __forceinline__ void take_half(int i, uint32_t part, uint32_t live, const uint32_t* ml, int mvx, int mvy, int px,
-                                          int py, uint32_t& best, int& bi) {
-  const uint32_t d = (group_sum<L>(part & live) >> kDsh) + mvc(ml, mv_bits(2 * mvx + h9_dx(i), 2 * mvy + h9_dy(i), 1, px, py));
-  if (d < best || (d == best && i < bi)) {
-    best = d;
-    bi = i;
-  }
-}
-template <int L>
-__device__ __forceinline__ void take_qtr(int i, uint32_t part, uint32_t live, const uint32_t* ml, int mvx, int mvy, int hx,
-                                         int hy, int px, int py, uint32_t& best, int& bi) {
-  const int qx = 2 * hx + q9_dx(i), qy = 2 * hy + q9_dy(i);
-  const uint32_t d = (group_sum<L>(part & live) >> kDsh) + mvc(ml, mv_bits(4 * mvx + qx, 4 * mvy + qy, 0, px, py));
-  if (d < best || (d == best && i < bi)) {
-    best = d;
-    bi = i;
-  }
-}
-
-typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t u32x3a __attribute__((ext_vector_type(3), aligned(4)));
-typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
-typedef __attribute__((address_space(1))) const u32x4a gu4;
-typedef __attribute__((address_space(1))) const u32x3a gu3;
-typedef __attribute__((address_space(1))) const u32x2a gu2;
 typedef __attribute__((address_space(1))) const uint16_t g_u16;
-
-// N dwords from byte address p, any alignment (gfx950 global memory runs unaligned).
-template <int N>
-__device__ __forceinline__ void ld_dw(const void* p, uint32_t (&o)[N]) {
-  const uint8_t* q = (const uint8_t*)p;
-  constexpr int K4 = N / 4 * 4;
-#pragma unroll
-  for (int k = 0; k < K4; k += 4) {
-    const u32x4a v = *(gu4*)(q + 4 * k);
-    o[k] = v.x; o[k + 1] = v.y; o[k + 2] = v.z; o[k + 3] = v.w;
-  }
-  if constexpr (N - K4 == 3) {
-    const u32x3a v = *(gu3*)(q + 4 * K4);
-    o[K4] = v.x; o[K4 + 1] = v.y; o[K4 + 2] = v.z;
-  } else if constexpr (N - K4 == 2) {
-    const u32x2a v = *(gu2*)(q + 4 * K4);
-    o[K4] = v.x; o[K4 + 1] = v.y;
-  } else if constexpr (N - K4 == 1) {
-    o[K4] = gld32(q + 4 * K4);
-  }
-}
 
 // Rows y0 .. y0+R-1, samples x0 .. x0 + 2N - 1 of a 10-bit picture as s' pairs, with the padded
 // picture's edge replication (TComPicYuv::extendPicBorder: coordinates clamped).
@@ -310,7 +204,7 @@ __device__ __forceinline__ void load_window(const PicDesc& pic, int x0, int y0, 
 #pragma unroll
     for (int r = 0; r < R; r++) {
       const int yy = clamp_i(y0 + r, 0, pic.height - 1);
-      ld_dw<N>(luma + (size_t)yy * pic.stride + x0, v[r]);
+      ld_bytes<N>(luma + (size_t)yy * pic.stride + x0, v[r]);
       if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
     }
   } else {
@@ -452,12 +346,6 @@ __device__ __forceinline__ void half_sides(uint32_t (&v)[UH + 8][(UW + 8) / 2], 
   }
 }
 
-typedef __attribute__((address_space(1))) const fme_job g_job;
-typedef __attribute__((address_space(1))) const int32_t g_i32;
-typedef __attribute__((address_space(1))) fme_result g_res;
-typedef __attribute__((address_space(1))) const int16_t g_i16;
-typedef __attribute__((address_space(1))) const uint32_t g_u32;
-
 // One lane: unit (ux, uy) of PU p of class (PW x PH), unit UW x UH; PUs of more than 64 units give a
 // lane two (top and bottom half), each candidate pass running once per half.
 template <int PW, int PH, int UW, int UH>
@@ -481,24 +369,20 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
   constexpr int EW = (UW + 2 + 1) / 2;         // EMI window pairs per row (cols -1 .. UW)
   constexpr int KW = UW / 2;                   // key pairs per row
 
-  const int lane = (int)__lane_id();
-  const int gl = wt * 64 + lane;
-  int p = gl / L;
-  const int u = gl - p * L;
-  const bool active = p < cls_cnt;
-  if (!active) p = cls_cnt - 1;
-  const uint32_t live = u < NUH ? ~0u : 0u;
-  const int uu = u < NUH ? u : NUH - 1;
-  const int ux = uu % UX, uy = uu / UX;
+  const LaneMap lm = lane_map<L, NUH, UX>(wt, cls_cnt);
+  const int lane = lm.lane, ux = lm.ux, uy = lm.uy;
+  const uint32_t live = lm.live;
 
-  const int jid = perm[cls_off + p];
+  const int jid = perm[cls_off + lm.p];
+  // (Keep this form of the job load, and the other one in fme_lane.hip: either change shifts every
+  // class's register assignment)
   const fme_job j = load_job(a, jid);
   auto ref_pic = [&]() FME_AI -> PicDesc {
     int rid = j.ref_id;
     asm volatile("" : "+v"(rid));
-    return g10_pics[rid];
+    return g_pics[rid];
   };
-  const uint32_t* const ml = g10_cost[j.lambda_id];
+  const uint32_t* const ml = g_cost[j.lambda_id];
   const bool kbuf = j.key_offset >= 0;
   const Metric met = {use_hadamard && !(j.flags & FME_JOB_LOSSLESS), kbuf, (lane & 1) ? 0xFFFFFFFFu : 0x00010001u,
                       (lane & 1) ? 0u : ~0u};
@@ -511,14 +395,14 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
     int ky = oy + h * kHalfRows;
     asm volatile("" : "+v"(ky));
     if (!kbuf) {
-      const PicDesc org = g10_pics[j.org_id];
+      const PicDesc org = g_pics[j.org_id];
       const uint16_t* ol = reinterpret_cast<const uint16_t*>(org.luma);
 #pragma unroll
-      for (int r = 0; r < UH; r++) ld_dw<KW>(ol + (size_t)(ky + r) * org.stride + ox, kraw[r]);
+      for (int r = 0; r < UH; r++) ld_bytes<KW>(ol + (size_t)(ky + r) * org.stride + ox, kraw[r]);
     } else {
       g_i16* kb = keys + (size_t)j.key_offset + (size_t)(ky - (int)j.y) * PW + ux * UW;
 #pragma unroll
-      for (int r = 0; r < UH; r++) ld_dw<KW>((const void*)(kb + r * PW), kraw[r]);
+      for (int r = 0; r < UH; r++) ld_bytes<KW>((const void*)(kb + r * PW), kraw[r]);
     }
 #pragma unroll
     for (int r = 0; r < UH; r++)
@@ -591,7 +475,7 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
       e9[pos] = v;
     }
     const int sx = mvx, sy = mvy;
-    uint32_t best = e9[0] + mvc(ml, mv_bits(sx, sy, 2, mvp_x, mvp_y));
+    uint32_t best = e9[0] + mv_cost(ml, mv_bits(sx, sy, 2, mvp_x, mvp_y));
     uint32_t best_cost = best - e9[0];
     int bx = sx, by = sy;
     const bool top = sy - 1 >= j.lt_y, bot = sy + 1 <= j.rb_y;
@@ -607,9 +491,10 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
           if (k == n_emi) emi[k] = d;
         n_emi++;
         if (d < best) {
-          const uint32_t cst = mvc(ml, mv_bits(sx + dx, sy + dy, 2, mvp_x, mvp_y));
-          if (d + cst < best) {
-            best = d + cst;
+          const uint32_t cst = mv_cost(ml, mv_bits(sx + dx, sy + dy, 2, mvp_x, mvp_y));
+          const uint32_t dc = d + cst;
+          if (dc < best) {
+            best = dc;
             best_cost = cst;
             bx = sx + dx;
             by = sy + dy;
@@ -621,11 +506,13 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
     mvx = bx;
     mvy = by;
   }
+  const int u = lm.u;
+  const bool active = lm.active;
   if (u == 0) {
-    g10_rec[wid][lane][1] = make_uint4(0u, 0u, cval, emi[0]);
-    g10_rec[wid][lane][2] = make_uint4(emi[1], emi[2], emi[3], emi[4]);
-    g10_rec[wid][lane][3] = make_uint4(emi[5], emi[6], emi[7], (uint32_t)n_emi);
-    g10_rec_jid[wid][lane] = !active ? -1 : jid;
+    g_rec[wid][lane][1] = make_uint4(0u, 0u, cval, emi[0]);
+    g_rec[wid][lane][2] = make_uint4(emi[1], emi[2], emi[3], emi[4]);
+    g_rec[wid][lane][3] = make_uint4(emi[5], emi[6], emi[7], (uint32_t)n_emi);
+    g_rec_jid[wid][lane] = !active ? -1 : jid;
   }
 
   // ---- the resident half: window rows -4..UH+3, cols -4..UW+3 around mv_int', key columns --------
@@ -652,6 +539,7 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
   };
   load_half(0);
   int cur = 0;
+  // One candidate pass over the PU: the resident half first, then (two units per lane) the other.
   auto over_halves = [&](auto&& pass, auto& d) FME_AI {
     pass(d);
     if constexpr (UPL == 2) {
@@ -674,19 +562,19 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
     const int qy[3] = {0, -2, 2};
     uint32_t d[3];
     over_halves([&](uint32_t (&dd)[3]) FME_AI { qpass<UW, UH, T, 0, 3>(v, K, met, 0, qy, dd); }, d);
-    take_half<L>(0, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(1, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(2, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, kDsh>(0, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, kDsh>(1, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, kDsh>(2, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
   }
   {
     uint32_t d[6];
     over_halves([&](uint32_t (&dd)[6]) FME_AI { half_sides<UW, UH, T>(v, K, met, dd); }, d);
-    take_half<L>(3, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(5, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(7, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(4, d[3], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(6, d[4], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
-    take_half<L>(8, d[5], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, kDsh>(3, d[0], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, kDsh>(5, d[1], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, kDsh>(7, d[2], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, kDsh>(4, d[3], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, kDsh>(6, d[4], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
+    take_half<L, kDsh>(8, d[5], live, ml, mvx, mvy, mvp_x, mvp_y, hbest, hbi);
   }
   const int hx = h9_dx(hbi), hy = h9_dy(hbi);
 
@@ -708,12 +596,12 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
     }
     uint32_t d[NQ];
     over_halves([&](uint32_t (&dd)[NQ]) FME_AI { qpass<UW, UH, T, kRuntime, NQ>(v, K, met, 2 * hx + kk - 1, qy, dd); }, d);
-    take_qtr<L>(q9_index(kk - 1, -1), d[0], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
+    take_qtr<L, kDsh>(q9_index(kk - 1, -1), d[0], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
     if constexpr (kk == 1) {
-      take_qtr<L>(q9_index(0, 1), d[1], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
+      take_qtr<L, kDsh>(q9_index(0, 1), d[1], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
     } else {
-      take_qtr<L>(q9_index(kk - 1, 0), d[1], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
-      take_qtr<L>(q9_index(kk - 1, 1), d[2], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
+      take_qtr<L, kDsh>(q9_index(kk - 1, 0), d[1], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
+      take_qtr<L, kDsh>(q9_index(kk - 1, 1), d[2], live, ml, mvx, mvy, hx, hy, mvp_x, mvp_y, qbest, qbi);
     }
   };
   static_for<0, 3>(qcol);
@@ -724,7 +612,7 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
   const uint32_t r_mv = (uint32_t)(uint16_t)mvx | ((uint32_t)(uint16_t)mvy << 16);
   const uint32_t r_hq = (uint32_t)(uint8_t)hx | ((uint32_t)(uint8_t)hy << 8) | ((uint32_t)(uint8_t)q9_dx(bq) << 16) |
                         ((uint32_t)(uint8_t)q9_dy(bq) << 24);
-  if (u == 0) g10_rec[wid][lane][0] = make_uint4(r_mv, 0u, r_hq, qbest);
+  if (u == 0) g_rec[wid][lane][0] = make_uint4(r_mv, 0u, r_hq, qbest);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -734,9 +622,9 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
     const int r = s0 * 16 + (lane >> 2);
     if (r < NP) {
       const int src = r * L;
-      const int rj = g10_rec_jid[wid][src];
+      const int rj = g_rec_jid[wid][src];
       if (rj >= 0) {
-        const uint4 q = g10_rec[wid][src][lane & 3];
+        const uint4 q = g_rec[wid][src][lane & 3];
         u32x4a o;
         o.x = q.x; o.y = q.y; o.z = q.z; o.w = q.w;
         *(gw4*)(reinterpret_cast<__attribute__((address_space(1))) uint8_t*>(outp + rj) + 16 * (lane & 3)) = o;
@@ -745,100 +633,29 @@ __device__ __attribute__((noinline)) void lane_unit10(const BatchArgs& a, const 
   }
 }
 
-__device__ __forceinline__ int xcc_id() { return __builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11)) & 7; }
-
 }  // namespace
 
-// The 8-bit lane kernel's classes and unit shapes (fme_lane.hip; the schedule's tile layout is
-// sched_params(), shared): 4x8 units, 4x4 units for 8x4 / 16x4 / 16x12.
-#define FME_L10_CLASSES(X)                                                                           \
-  X(0, 4, 8, 4, 8) X(3, 4, 16, 4, 8) X(1, 8, 4, 4, 4) X(4, 16, 4, 4, 4) X(2, 8, 8, 4, 8)              \
-  X(5, 8, 16, 4, 8) X(6, 16, 8, 4, 8) X(9, 16, 16, 4, 8) X(10, 8, 32, 4, 8) X(11, 32, 8, 4, 8)        \
-  X(12, 16, 32, 4, 8) X(13, 32, 16, 4, 8) X(16, 32, 32, 4, 8) X(17, 16, 64, 4, 8) X(18, 64, 16, 4, 8) \
-  X(19, 32, 64, 4, 8) X(20, 64, 32, 4, 8) X(23, 64, 64, 4, 8) X(7, 12, 16, 4, 8) X(8, 16, 12, 4, 4)   \
-  X(14, 24, 32, 4, 8) X(15, 32, 24, 4, 8) X(21, 48, 64, 4, 8) X(22, 64, 48, 4, 8)
-
-// One persistent kernel for every class, the 8-bit kernel's work order: a workgroup claims four
-// consecutive wave tiles per atomic from its XCD's queue (Schedule::xq), then the other XCDs'.
+// One persistent kernel for every class, the 8-bit kernel's classes, unit shapes and work order
+// (FME_LANE_CLASSES; lane_claim_loop, fme_lane_common.h).
 #define FME_CASE10(ID, PW_, PH_, UW_, UH_)                                                 \
   case ID:                                                                                 \
     lane_unit10<PW_, PH_, UW_, UH_>(a, w.perm, sc->class_off[ID], sc->class_cnt[ID], wt, wid); \
     break;
-__global__ __launch_bounds__(kL10NT) __attribute__((amdgpu_waves_per_eu(FME_L10_WAVES)))
+__global__ __launch_bounds__(kLaneNT) __attribute__((amdgpu_waves_per_eu(FME_L10_WAVES)))
 void k_search_lane10(BatchArgs a, WorkBufs w) {
-  constexpr int S = FME_LANE_SUBBANDS;
-  const Schedule* __restrict__ sc = w.sched;
-  if (sc->invalid) return;   // rejected batch: the tail marks every record
-  int32_t* ctr = w.tile_ctr;
-  __shared__ int32_t s_xq[8][S][kNumClasses + 1];
-  {
-    const uint32_t* ps = reinterpret_cast<const uint32_t*>(a.pics);
-    uint32_t* pd = reinterpret_cast<uint32_t*>(g10_pics);
-    for (int i = threadIdx.x; i < (int)(sizeof(g10_pics) / 4); i += kL10NT) pd[i] = ps[i];
-    for (int i = threadIdx.x; i < FME_MAX_LAMBDAS * kCostBits; i += kL10NT)
-      g10_cost[i / kCostBits][i % kCostBits] = simd::mv_cost(a.mlambda[i / kCostBits], (uint32_t)(i % kCostBits));
-    for (int i = threadIdx.x; i < 8 * S * (kNumClasses + 1); i += kL10NT) (&s_xq[0][0][0])[i] = (&sc->xq[0][0][0])[i];
-  }
-  const int home = xcc_id(), wid = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  constexpr int kGroup = kL10NT / 64;
-  __shared__ int32_t claim[2];
-  int x = home, tried = 0, par = 0;
-  if (threadIdx.x == 0) claim[0] = atomicAdd(&ctr[x], 1);
-  __syncthreads();
-  int t = __builtin_amdgcn_readfirstlane(claim[0]);
-  while (true) {
-    const int len = s_xq[x][S - 1][kNumClasses];
-    if (kGroup * t >= len) {
-      if (++tried == 8) break;
-      x = (home + tried) & 7;
-      par ^= 1;
-      if (threadIdx.x == 0) claim[par] = atomicAdd(&ctr[x], 1);
-      __syncthreads();
-      t = __builtin_amdgcn_readfirstlane(claim[par]);
-      continue;
+  if (w.sched->invalid) return;   // rejected batch: the tail marks every record
+  lane_claim_loop<kLaneNT>(a, w, [&](const Schedule* sc, int c, int wt, int wid) FME_AI {
+    switch (c) {
+      FME_LANE_CLASSES(FME_CASE10)
+      default: break;
     }
-    int nxt = 0;
-    if (threadIdx.x == 0) nxt = atomicAdd(&ctr[x], 1);
-    const int tw = kGroup * t + wid;
-    if (tw < len) {
-      int q = 0, c = 0;
-      while (q < S - 1 && tw >= s_xq[x][q][kNumClasses]) q++;
-      while (c < kNumClasses - 1 && tw >= s_xq[x][q][c + 1]) c++;
-      const int ci = c;   // queue position -> class
-      c = lane_class_at(ci);
-      const int nt = sc->prefix[c + 1] - sc->prefix[c];
-      const int lo = (int)(((long long)nt * (x * S + q)) / (8 * S));
-      const int wt = __builtin_amdgcn_readfirstlane(lo + (tw - s_xq[x][q][ci]));
-      switch (c) {
-        FME_L10_CLASSES(FME_CASE10)
-        default: break;
-      }
-    }
-    par ^= 1;
-    if (threadIdx.x == 0) claim[par] = nxt;
-    __syncthreads();
-    t = __builtin_amdgcn_readfirstlane(claim[par]);
-  }
+  });
 }
 #undef FME_CASE10
 
 hipError_t launch_search_lane10(const BatchArgs& a, const WorkBufs& w, hipStream_t s) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    cus = cu_count(dev);
-  }
   if (a.n <= 0) return hipSuccess;
-  int max_l = 0, classes = 0;
-  for (int c = 0; c < kNumClasses; c++)
-    if (lane_lanes_per_pu(c)) {
-      max_l = std::max(max_l, lane_lanes_per_pu(c));
-      classes++;
-    }
-  const long long waves = ((long long)a.n * max_l + 63) / 64 + classes;
-  const int blocks = (int)std::min<long long>((waves + kL10NT / 64 - 1) / (kL10NT / 64), 4LL * cus);
-  hipLaunchKernelGGL(k_search_lane10, dim3(blocks), dim3(kL10NT), 0, s, a, w);
+  hipLaunchKernelGGL(k_search_lane10, dim3(lane_grid(a.n, 0)), dim3(kLaneNT), 0, s, a, w);
   return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
-// fme_simd.h — per-lane integer helpers shared by the search kernels (fme_search.hip,
-// fme_lane.hip): MV cost (TComRdCost), packed int16/int8 arithmetic, byte funnels and
+// fme_simd.h — per-lane integer helpers shared by the kernels (fme_lane.hip, fme_lane10.hip,
+// fme_tz.hip, fme_mc.hip, fme_kernels.hip): MV cost (TComRdCost), packed int16/int8 arithmetic, byte funnels and
 // transposes, HEVC luma taps, and the packed SATD/SAD of 4x4 / 8x8 tiles.
 #pragma once
 
