@@ -145,6 +145,10 @@ int fme_destroy(fme_ctx* c) {
   c->d_sse_tasks.release(); c->d_sse_out.release(); c->d_sse_invalid.release();
   for (auto& e : c->ev_sse)
     if (e) (void)hipEventDestroy(e);
+  c->d_surf_jobs.release(); c->d_surf_probe.release(); c->d_surf_out.release(); c->d_surf_pick.release();
+  c->d_surf_invalid.release();
+  for (auto& e : c->ev_surf)
+    if (e) (void)hipEventDestroy(e);
   c->d_pics.release(); c->d_mlambda.release(); c->d_keys.release(); c->d_nn.release(); c->d_net.release();
   c->d_jobs.release(); c->d_res.release(); c->d_mv.release(); c->koff.release(); c->cls.release(); c->perm.release();
   c->counts.release(); c->blk_agg.release(); c->blk_prefix.release(); c->nn_state.release();

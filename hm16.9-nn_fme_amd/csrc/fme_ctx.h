@@ -169,6 +169,16 @@ struct fme_ctx {
   hipStream_t sse_stream = nullptr;
   hipEvent_t ev_sse[2] = {nullptr, nullptr};
   bool sse_timed = false;
+  // cost surface (fme_surface.cpp): staging for the host entry point, the invalid-job counter, the
+  // stream of the last launch, timing events
+  fme::DevBuf<fme_job> d_surf_jobs;
+  fme::DevBuf<uint8_t> d_surf_probe;     // [n][2]
+  fme::DevBuf<fme_surface> d_surf_out;
+  fme::DevBuf<fme_surface_pick> d_surf_pick;
+  fme::DevBuf<int32_t> d_surf_invalid;
+  hipStream_t surf_stream = nullptr;
+  hipEvent_t ev_surf[2] = {nullptr, nullptr};
+  bool surf_timed = false;
   // integer search: staging for the host entry point, timing events
   fme::DevBuf<fme_tz_ext> d_tz_ext;
   fme::DevBuf<uint32_t> d_tz_sad;

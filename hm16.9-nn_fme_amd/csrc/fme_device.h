@@ -8,6 +8,7 @@
 #include "../../include/fme.h"
 #include "../../include/fme_merge.h"
 #include "../../include/fme_skip.h"
+#include "../../include/fme_surface.h"
 #include "fme_srv_pack.h"
 
 // 1: the bulk integer search stages each (kernel, reference, CTU) group's search area in LDS
@@ -134,6 +135,24 @@ struct SseArgs {
   int32_t bit_depth;          // 8, or 10: uint16 planes, each sample's square >> 4
 };
 hipError_t launch_pred_sse(const SseArgs& a, hipStream_t s);
+
+// One cost-surface launch (fme_surface.hip k_cost_surface): the 49 quarter-pel distortions and costs
+// around each job's integer MV (include/fme_surface.h).
+struct SurfArgs {
+  const fme_job* jobs;
+  const uint8_t* probe;       // [n][2] position indices, or null: none
+  fme_surface* surf;          // per job, or null; 0xFFFFFFFF in every word of an invalid job
+  fme_surface_pick* pick;     // per job, or null
+  const PicDesc* pics;
+  const double* mlambda;      // [FME_MAX_LAMBDAS]
+  const int16_t* keys;
+  int64_t n_keys;
+  int32_t* invalid;           // count of invalid jobs
+  int32_t n;
+  int32_t bit_depth;          // 8, or 10: uint16 planes, the PU's sum >> 2
+  int32_t use_hadamard;       // HADME (fme_config.use_hadamard)
+};
+hipError_t launch_cost_surface(const SurfArgs& a, hipStream_t s);
 
 
 // One batch as the device sees it.

@@ -284,6 +284,30 @@ std::vector<fme_skip_res> SkipEstimator::run(const fme_skip_params& params) {
   return res;
 }
 
+// ---- CostSurface --------------------------------------------------------------------------
+
+int CostSurface::add(const fme_job& job, uint8_t probe0, uint8_t probe1) {
+  jobs_.push_back(job);
+  probes_.push_back(probe0);
+  probes_.push_back(probe1);
+  return (int)jobs_.size() - 1;
+}
+
+std::vector<fme_surface_pick> CostSurface::run(std::vector<fme_surface>* surfaces) {
+  std::vector<fme_job> jobs;
+  std::vector<uint8_t> probes;
+  jobs.swap(jobs_);   // the queue is empty afterwards, also when the call throws
+  probes.swap(probes_);
+  std::vector<fme_surface_pick> picks(jobs.size());
+  if (surfaces) surfaces->assign(jobs.size(), fme_surface{});
+  std::lock_guard<std::mutex> lk(search_.mutex());
+  if (!jobs.empty())
+    check(fme_cost_surface(search_.ctx(), jobs.data(), reinterpret_cast<const uint8_t(*)[2]>(probes.data()),
+                           surfaces ? surfaces->data() : nullptr, picks.data(), (int)jobs.size(), nullptr),
+          "fme_cost_surface");
+  return picks;
+}
+
 // ---- InterSearchP -------------------------------------------------------------------------
 
 int InterSearchP::add(const fme_pu_req& req) {

@@ -72,8 +72,17 @@ def nn_inputs(jobs, results, state_in=None):
     return e, c, pu_h, pu_w, out
 
 
-def records(jobs, results, state_in=None):
-    """The SSE.csv records of one fme_refine batch (RECORD_DTYPE[n]) and the carried-out state."""
+def records(jobs, results, state_in=None, label="search", surface=None):
+    """The SSE.csv records of one fme_refine batch (RECORD_DTYPE[n]) and the carried-out state.
+
+    label "search" (the default, the reference's): y is OUT_CLASS of the two-stage search's pick.
+    label "surface_min": y is the class of the least of the 49 costs (first index on a tie) of
+    `surface`, the jobs' cost surfaces centred on mv_int (nnfme.surface: SURFACE_DTYPE[n] or
+    cost[n, 49]), for retraining on labels the two-stage search cannot reach."""
+    if label not in ("search", "surface_min"):
+        raise ValueError(f"records: unknown label {label!r}")
+    if label == "surface_min" and (surface is None or len(surface) != len(jobs)):
+        raise ValueError("records: label 'surface_min' needs one cost surface per job")
     e, c, _, _, out = nn_inputs(jobs, results, state_in)
     r = np.zeros(len(jobs), RECORD_DTYPE)
     for s, name in enumerate(("top_left", "top_center", "top_right", "left")):
@@ -83,7 +92,12 @@ def records(jobs, results, state_in=None):
         r[name] = e[:, 4 + s]
     r["Height"] = jobs["h"]
     r["Width"] = jobs["w"]
-    r["y"] = out_class(results["half_x"], results["half_y"], results["qtr_x"], results["qtr_y"])
+    if label == "surface_min":
+        a = np.asarray(surface)
+        cost = (a["cost"] if a.dtype.names else a).reshape(len(jobs), 49)
+        r["y"] = np.argmin(cost, axis=1)
+    else:
+        r["y"] = out_class(results["half_x"], results["half_y"], results["qtr_x"], results["qtr_y"])
     return r, out
 
 

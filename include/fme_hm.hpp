@@ -35,6 +35,7 @@
 #include "fme.h"
 #include "fme_merge.h"
 #include "fme_skip.h"
+#include "fme_surface.h"
 
 namespace fme_hm {
 
@@ -191,6 +192,27 @@ class SkipEstimator {
  private:
   FracSearch& search_;
   std::vector<fme_skip_req> reqs_;
+};
+
+// The sub-pel cost surface (include/fme_surface.h): per fme_job the cost of all 49 quarter-pel
+// positions within +-3/4 pel of its integer MV, in xPatternSearchFracDIF's terms (its prediction,
+// its distortion, its MV cost): what the search's pick, NN_pred()'s class and the true minimum
+// cost against each other.  The caller queues one job per PU, optionally with two positions to
+// probe (e.g. the NN class), and gets one pick per job and, on request, the surfaces; the pictures,
+// lambda slots and keys are the search's.
+class CostSurface {
+ public:
+  explicit CostSurface(FracSearch& search) : search_(search) {}
+  // index of the job in the pending batch; probes: position indices 0..48 (FME_SURF_INDEX)
+  int add(const fme_job& job, uint8_t probe0 = FME_SURF_NO_PROBE, uint8_t probe1 = FME_SURF_NO_PROBE);
+  int pending() const { return (int)jobs_.size(); }
+  // the queued jobs in order; clears the queue.  surfaces: null, or receives one fme_surface per job
+  std::vector<fme_surface_pick> run(std::vector<fme_surface>* surfaces = nullptr);
+
+ private:
+  FracSearch& search_;
+  std::vector<fme_job> jobs_;
+  std::vector<uint8_t> probes_;   // two per job
 };
 
 // TEncSearch::predInterSearch's uni-directional PU / reference loop for P slices
