@@ -1437,7 +1437,7 @@ static int mc_launch(fme_ctx* c, const fme_mc_job* d_jobs, int n, uint8_t* y, in
   a.c_stride = cs;
   a.width = width;
   a.height = height;
-  a.bit_depth = c->cfg.bit_depth;   // 10: uint16 planes, strides in samples (k_mc10)
+  a.bit_depth = c->cfg.bit_depth;   // 10: uint16 planes, strides in samples (k_mc<true>)
   if (c->profiling) {
     if (!c->ev_mc[0]) {
       HIP_TRY(hipEventCreate(&c->ev_mc[0]));

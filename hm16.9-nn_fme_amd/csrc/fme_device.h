@@ -56,6 +56,15 @@ struct PicDesc {
   int32_t pad_;
 };
 
+// The launch of a kernel that is built per bit depth (template <bool k10>): the 10-bit instance
+// when the arguments say so, nothing when there is no work.
+template <class Args>
+inline hipError_t launch_by_depth(void (*k8)(Args), void (*k10)(Args), int grid, int block, const Args& a,
+                                  hipStream_t s) {
+  if (a.n > 0) hipLaunchKernelGGL(a.bit_depth > 8 ? k10 : k8, dim3(grid), dim3(block), 0, s, a);
+  return hipGetLastError();
+}
+
 // One motion-compensation launch (fme_mc.hip).
 struct McArgs {
   const fme_mc_job* jobs;
@@ -84,7 +93,7 @@ struct AmvpArgs {
   const PicDesc* pics;
   uint32_t* sad;
   int32_t n;
-  int32_t bit_depth;          // 8, or 10: uint16 planes (k_amvp_sad<10>)
+  int32_t bit_depth;          // 8, or 10: uint16 planes (k_amvp_sad<true>)
 };
 hipError_t launch_amvp_sad(const AmvpArgs& a, hipStream_t s);
 
@@ -107,7 +116,7 @@ struct BiKeyArgs {
   int32_t n;
   int32_t* invalid;           // device-resident requests: validated here, rejected ones counted
   int64_t n_keys;             // (then) the key buffer's length
-  int32_t bit_depth;          // 8, or 10: uint16 planes, ClipForBiPredMe to 0..1023 (k_bi_key<10>)
+  int32_t bit_depth;          // 8, or 10: uint16 planes, ClipForBiPredMe to 0..1023 (k_bi_key<true>)
 };
 hipError_t launch_bi_key(const BiKeyArgs& a, hipStream_t s);
 

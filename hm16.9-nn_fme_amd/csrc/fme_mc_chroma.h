@@ -24,21 +24,25 @@ __device__ __forceinline__ uint32_t chroma_taps(int f) {
 }
 
 // One list's prediction of the 2x2 unit of component comp (1 Cb, 2 Cr) at chroma position (bx, by)
-// (integer MV applied) with the eighth-pel fractions (fx, fy), 8-bit planes.
-__device__ __forceinline__ void chroma_pred8(const PicDesc& p, int comp, int bx, int by, int fx, int fy, bool uni,
-                                             int (&o)[2][2]) {
+// (integer MV applied) with the eighth-pel fractions (fx, fy).  (The depth dispatch stands here and
+// not behind unit_pred: through that extra layer k_pred_sse<false> allocates 169 VGPRs instead of
+// 168 and loses its third wave per SIMD.)
+template <bool k10>
+__device__ __forceinline__ void chroma_pred(const PicDesc& p, int comp, int bx, int by, int fx, int fy, bool uni,
+                                            int (&o)[2][2]) {
   const Plane pl{comp == 1 ? p.cb : p.cr, p.cstride, p.width >> 1, p.height >> 1};
-  UnitWin<4, 2> w;
-  w.load(pl, ((p.cstride | (int)(uintptr_t)pl.p) & 3) == 0, bx, by);
-  w.pred(chroma_taps(fx), 0u, chroma_taps(fy), 0u, uni, o);
+  if constexpr (k10) {
+    pred10<4, 2>(pl, bx, by, chroma_taps(fx), 0u, chroma_taps(fy), 0u, uni, o);
+  } else {
+    UnitWin<4, 2> w;
+    w.load(pl, ((p.cstride | (int)(uintptr_t)pl.p) & 3) == 0, bx, by);
+    w.pred(chroma_taps(fx), 0u, chroma_taps(fy), 0u, uni, o);
+  }
 }
-
-// The same on uint16 planes (bit depth 10).
-__device__ __forceinline__ void chroma_pred10(const PicDesc& p, int comp, int bx, int by, int fx, int fy, bool uni,
-                                              int (&o)[2][2]) {
-  const Plane16 pl{reinterpret_cast<const uint16_t*>(comp == 1 ? p.cb : p.cr), p.cstride, p.width >> 1,
-                   p.height >> 1};
-  pred10<4, 2>(pl, bx, by, chroma_taps(fx), 0u, chroma_taps(fy), 0u, uni, o);
+// One list's prediction of the 2x2 unit of component comp at chroma position (x, y).
+template <bool k10>
+__device__ __forceinline__ void list_chroma(const ListMotion& m, int comp, int x, int y, bool uni, int (&o)[2][2]) {
+  chroma_pred<k10>(m.pic, comp, x + m.cix, y + m.ciy, m.cfx, m.cfy, uni, o);
 }
 
 }  // namespace mcl

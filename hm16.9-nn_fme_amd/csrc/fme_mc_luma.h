@@ -1,7 +1,10 @@
-// fme_mc_luma.h — xPredInterBlk's building blocks shared by the motion-compensation kernels
-// (fme_mc.hip), the prediction-error kernel (fme_merge.hip) and the skip-check kernel (fme_skip.hip):
-// the luma interpolation taps, clipMv, the edge-replicated reference window of one output unit and
-// its two-stage filter, at 8 and 10 bits.
+// fme_mc_luma.h — xPredInterBlk's building blocks shared by the prediction kernels: motion
+// compensation and the producers' luma stages (fme_mc.hip), the prediction error (fme_merge.hip), the
+// skip check (fme_skip.hip) and the cost surface (fme_surface.hip: taps and window only).  The luma
+// interpolation taps, clipMv, the edge-replicated reference window of one output unit and its
+// two-stage filter at 8 and 10 bits behind one depth-dispatching predictor (unit_pred), the
+// resolution of a PU's motion into its predicted lists (resolve_lists, ListMotion), the prediction
+// of a unit from up to two lists (pred_lists, add_avg) and the checks the validity predicates share.
 // The derivations are in fme_mc.hip's module header.
 #pragma once
 
@@ -137,22 +140,20 @@ struct UnitWin {
 // filterCopy's 16 s'), the second uni (isLast): ((sum c h + 512) >> 10) + 512 clipped to 0..1023,
 // bi (!isLast): (sum c h) >> 6, which is HM's 14-bit value for every fraction pair (a zero fraction
 // is the identity: (64 h) >> 6 = h, (16 sum c s') >> 6 = (sum c s') >> 2).  TComYuv::addAvg at
-// bitDepth 10: (p0 + p1 + 16400) >> 5 clipped (shift 14 + 1 - 10, offset 16 + 2 * 8192).
-struct Plane16 {
-  const uint16_t* p;
-  int stride, w, h;
-};
+// bitDepth 10 shifts by 14 + 1 - 10 after adding 16 + 2 * 8192 (add_avg).
 typedef __attribute__((address_space(1))) const uint16_t gu16c;
 
+// pl.p points at uint16 samples, pl.stride counts samples.
 template <int N, int U>
-__device__ __forceinline__ void pred10(const Plane16& pl, int bx, int by, uint32_t hlo, uint32_t hhi, uint32_t vlo,
+__device__ __forceinline__ void pred10(const Plane& pl, int bx, int by, uint32_t hlo, uint32_t hhi, uint32_t vlo,
                                        uint32_t vhi, bool uni, int (&out)[U][U]) {
   constexpr int R = U + N - 1;
   const int x0 = bx - (N / 2 - 1), y0 = by - (N / 2 - 1);
+  const uint16_t* px = reinterpret_cast<const uint16_t*>(pl.p);
   int h[R][U];
 #pragma unroll
   for (int r = 0; r < R; r++) {
-    const gu16c* row = (const gu16c*)(pl.p + (size_t)clamp_i(y0 + r, 0, pl.h - 1) * pl.stride);
+    const gu16c* row = (const gu16c*)(px + (size_t)clamp_i(y0 + r, 0, pl.h - 1) * pl.stride);
     int sv[R];
 #pragma unroll
     for (int c = 0; c < R; c++) sv[c] = (int)row[clamp_i(x0 + c, 0, pl.w - 1)] - 512;
@@ -173,6 +174,132 @@ __device__ __forceinline__ void pred10(const Plane16& pl, int bx, int by, uint32
       for (int k = 0; k < N; k++) sum += h[y + k][c] * tap_of(vlo, vhi, k);
       out[y][c] = uni ? clamp_i(((sum + 512) >> 10) + 512, 0, 1023) : (sum >> 6);
     }
+}
+
+// Sample i of a plane at either depth (k10: plane holds uint16 samples).
+template <bool k10>
+__device__ __forceinline__ int ld_sample(const uint8_t* plane, size_t i) {
+  if constexpr (k10) return (int)((const gu16c*)reinterpret_cast<const uint16_t*>(plane))[i];
+  else return (int)gld8(plane + i);
+}
+
+// One U x U unit of one list at either depth (k10: uint16 planes, pred10; else UnitWin).
+template <bool k10, int N, int U>
+__device__ __forceinline__ void unit_pred(const Plane& pl, bool aligned, int bx, int by, uint32_t hlo, uint32_t hhi,
+                                          uint32_t vlo, uint32_t vhi, bool uni, int (&out)[U][U]) {
+  if constexpr (k10) {
+    pred10<N, U>(pl, bx, by, hlo, hhi, vlo, vhi, uni, out);
+  } else {
+    UnitWin<N, U> w;
+    w.load(pl, aligned, bx, by);
+    w.pred(hlo, hhi, vlo, vhi, uni, out);
+  }
+}
+
+// The 4x4 luma unit at plane position (bx, by) (integer MV applied), quarter-pel fractions (fx, fy).
+template <bool k10>
+__device__ __forceinline__ void luma_pred(const Plane& pl, bool aligned, int bx, int by, int fx, int fy, bool uni,
+                                          int (&o)[4][4]) {
+  uint32_t hlo, hhi, vlo, vhi;
+  luma_taps(fx, hlo, hhi);
+  luma_taps(fy, vlo, vhi);
+  unit_pred<k10, 8, 4>(pl, aligned, bx, by, hlo, hhi, vlo, vhi, uni, o);
+}
+__device__ __forceinline__ Plane luma_plane(const PicDesc& p) { return Plane{p.luma, p.stride, p.width, p.height}; }
+__device__ __forceinline__ bool dword_rows(const uint8_t* p, int stride) { return ((stride | (int)(uintptr_t)p) & 3) == 0; }
+
+// One predicted list of a PU's motion: its picture and the clipped MV split as xPredInterBlk does
+// (shift 2 + csx, fraction mask (4 << csx) - 1) for luma and 4:2:0 chroma.
+struct ListMotion {
+  PicDesc pic;
+  int lix, liy, lfx, lfy;   // luma integer offset, quarter-pel fraction
+  int cix, ciy, cfx, cfy;   // chroma integer offset, eighth-pel fraction (unused by luma-only callers)
+};
+
+// The lists a PU's motion predicts from (flags: FME_MC_L0 | FME_MC_L1), in list order, into lm[0 .. nl):
+// clipMv against the CU origin and, where the caller lets it apply, xCheckIdenticalMotion
+// (TComPrediction.cpp:476-492): both lists on one picture with one MV -> xPredInterUni(REF_PIC_LIST_0).
+// Selects, not reads indexed by the list: the job stays in registers.
+__device__ __forceinline__ int resolve_lists(uint32_t flags, const uint8_t (&ref_id)[2], const int16_t (&mv)[2][2],
+                                             int cu_x, int cu_y, const PicDesc* pics, bool check_identical,
+                                             ListMotion (&lm)[2]) {
+  const int r0 = ref_id[0], r1 = ref_id[1], x0 = mv[0][0], y0 = mv[0][1], x1 = mv[1][0], y1 = mv[1][1];
+  int nl = ((flags & FME_MC_L0) ? 1 : 0) + ((flags & FME_MC_L1) ? 1 : 0);
+  if (check_identical && nl == 2 && r0 == r1 && x0 == x1 && y0 == y1) nl = 1;
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    if (k >= nl) break;
+    const bool l1 = k == 1 || !(flags & FME_MC_L0);   // the k-th predicted list is list 1
+    ListMotion& m = lm[k];
+    m.pic = pics[l1 ? r1 : r0];
+    int mx = l1 ? x1 : x0, my = l1 ? y1 : y0;
+    clip_mv(mx, my, m.pic.width, m.pic.height, cu_x, cu_y);
+    m.lix = mx >> 2;
+    m.liy = my >> 2;
+    m.lfx = mx & 3;
+    m.lfy = my & 3;
+    m.cix = mx >> 3;
+    m.ciy = my >> 3;
+    m.cfx = mx & 7;
+    m.cfy = my & 7;
+  }
+  return nl;
+}
+
+// One list's prediction of the 4x4 luma unit at (x, y).
+template <bool k10>
+__device__ __forceinline__ void list_luma(const ListMotion& m, int x, int y, bool uni, int (&o)[4][4]) {
+  luma_pred<k10>(luma_plane(m.pic), dword_rows(m.pic.luma, m.pic.stride), x + m.lix, y + m.liy, m.lfx, m.lfy, uni, o);
+}
+
+// TComYuv::addAvg of the two lists' 14-bit values (TComYuv.cpp:354-415): shift 15 - bitDepth, offset
+// half of it + 2 * 8192, clipped to the bit depth.
+template <bool k10>
+__device__ __forceinline__ int add_avg(int p0, int p1) {
+  return k10 ? clamp_i((p0 + p1 + 16400) >> 5, 0, 1023) : clamp_i((p0 + p1 + 16448) >> 7, 0, 255);
+}
+
+// A unit's prediction from its nl (1 or 2) lists.  one(k, o) predicts list k into o: clipped samples
+// when it is the only list (uni), else 14-bit values.  p = the only list's samples or add_avg of the
+// two; l0 and l1 keep the values of list 0 and of the last list predicted (weighted prediction
+// combines those itself).
+template <bool k10, class F, int U>
+__device__ __forceinline__ void pred_lists(int nl, F one, int (&p)[U][U], int (&l0)[U][U], int (&l1)[U][U]) {
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    if (k >= nl) break;
+    one(k, l1);
+#pragma unroll
+    for (int r = 0; r < U; r++)
+#pragma unroll
+      for (int c = 0; c < U; c++) {
+        if (k == 0) l0[r][c] = l1[r][c];
+        p[r][c] = k == 0 ? l1[r][c] : add_avg<k10>(p[r][c], l1[r][c]);
+      }
+  }
+}
+template <bool k10, class F, int U>
+__device__ __forceinline__ void pred_lists(int nl, F one, int (&p)[U][U]) {
+  int l0[U][U], l1[U][U];
+  pred_lists<k10>(nl, one, p, l0, l1);
+}
+
+// What the validity predicates of the prediction kernels share: a PU is 4..64 samples in steps of 4,
+// and every predicted list names a pw x ph picture that has luma (and chroma where asked).
+__device__ __forceinline__ bool pu_shape_ok(int w, int h) {
+  return w >= 4 && h >= 4 && w <= 64 && h <= 64 && !(w & 3) && !(h & 3);
+}
+__device__ __forceinline__ bool ref_ok(bool used, int id, const PicDesc* pics, int pw, int ph, bool chroma) {
+  if (!used) return true;
+  if (id >= FME_MAX_PICTURES) return false;
+  const PicDesc& p = pics[id];
+  return p.luma && (!chroma || (p.cb && p.cr)) && p.width == pw && p.height == ph;
+}
+// (no loop over the lists: a read indexed by the list would put the job into scratch)
+__device__ __forceinline__ bool refs_ok(uint32_t flags, const uint8_t (&ref_id)[2], const PicDesc* pics, int pw, int ph,
+                                        bool chroma) {
+  return ref_ok(flags & FME_MC_L0, ref_id[0], pics, pw, ph, chroma) &&
+         ref_ok(flags & FME_MC_L1, ref_id[1], pics, pw, ph, chroma);
 }
 
 }  // namespace mcl

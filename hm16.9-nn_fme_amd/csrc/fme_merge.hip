@@ -37,8 +37,7 @@ using namespace mcl;
 using namespace xlane;
 
 constexpr int kPeBlock = 256;
-constexpr int kPeTasks = 64;   // consecutive tasks per workgroup, set up by its first wave
-enum { kPeSad = 0, kPeHad4 = 1, kPeHad8 = 2 };
+constexpr int kPeTasks = kGroupTasks;   // consecutive tasks per workgroup, set up by its first wave
 
 // Per-task state shared by the workgroup (LDS), filled by one thread per task.
 struct PeInfo {
@@ -54,61 +53,22 @@ struct PeInfo {
 };
 
 __device__ __forceinline__ bool pe_task_valid(const PeArgs& a, const fme_pe_task& t) {
-  if (t.w < 4 || t.h < 4 || t.w > 64 || t.h > 64 || (t.w & 3) || (t.h & 3)) return false;
+  if (!pu_shape_ok(t.w, t.h)) return false;
   if (!(t.flags & (FME_MC_L0 | FME_MC_L1)) || (t.flags & ~(FME_MC_L0 | FME_MC_L1 | FME_PE_LOSSLESS))) return false;
   if (t.org_id >= FME_MAX_PICTURES) return false;
   const PicDesc& o = a.pics[t.org_id];
   if (!o.luma || (int)t.x + t.w > o.width || (int)t.y + t.h > o.height) return false;
-  for (int l = 0; l < 2; l++) {
-    if (!(t.flags & (1u << l))) continue;
-    if (t.ref_id[l] >= FME_MAX_PICTURES) return false;
-    const PicDesc& p = a.pics[t.ref_id[l]];
-    if (!p.luma || p.width != o.width || p.height != o.height) return false;
-  }
-  return true;
-}
-
-// Unnormalised 2-D 4x4 Hadamard in place (rows, then columns).
-__device__ __forceinline__ void had4x4(int (&d)[4][4]) {
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int a = d[r][0] + d[r][1], b = d[r][0] - d[r][1], c = d[r][2] + d[r][3], e = d[r][2] - d[r][3];
-    d[r][0] = a + c; d[r][1] = b + e; d[r][2] = a - c; d[r][3] = b - e;
-  }
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    const int a = d[0][c] + d[1][c], b = d[0][c] - d[1][c], e = d[2][c] + d[3][c], f = d[2][c] - d[3][c];
-    d[0][c] = a + e; d[1][c] = b + f; d[2][c] = a - e; d[3][c] = b - f;
-  }
+  return refs_ok(t.flags, t.ref_id, a.pics, o.width, o.height, false);
 }
 
 // The prediction of the 4x4 unit at (x, y): both lists in registers, averaged (k_mc's luma block).
 template <bool k10>
 __device__ __forceinline__ void pe_predict(const PeInfo& in, int x, int y, int (&p)[4][4]) {
   const bool uni = in.nl == 1;
-  int o[4][4];
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    if (k >= in.nl) break;
-    uint32_t hlo, hhi, vlo, vhi;
-    luma_taps(in.fx[k], hlo, hhi);
-    luma_taps(in.fy[k], vlo, vhi);
-    if constexpr (k10) {
-      pred10<8, 4>(Plane16{reinterpret_cast<const uint16_t*>(in.ref[k]), in.rstride[k], in.pw, in.ph}, x + in.ix[k],
-                   y + in.iy[k], hlo, hhi, vlo, vhi, uni, o);
-    } else {
-      UnitWin<8, 4> w;
-      w.load(Plane{in.ref[k], in.rstride[k], in.pw, in.ph}, in.ral[k] != 0, x + in.ix[k], y + in.iy[k]);
-      w.pred(hlo, hhi, vlo, vhi, uni, o);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        if constexpr (k10) p[r][c] = k == 0 ? o[r][c] : clamp_i((p[r][c] + o[r][c] + 16400) >> 5, 0, 1023);
-        else p[r][c] = k == 0 ? o[r][c] : clamp_i((p[r][c] + o[r][c] + 16448) >> 7, 0, 255);
-      }
-  }
+  pred_lists<k10>(in.nl, [&](int k, int (&o)[4][4]) {
+    luma_pred<k10>(Plane{in.ref[k], in.rstride[k], in.pw, in.ph}, in.ral[k] != 0, x + in.ix[k], y + in.iy[k], in.fx[k],
+                   in.fy[k], uni, o);
+  }, p);
 }
 
 // d = org - pred of the unit at (x, y) (inside the original: the task was validated)
@@ -137,7 +97,7 @@ __device__ __forceinline__ void pe_diff(const PeInfo& in, int x, int y, const in
 template <bool k10>
 __global__ __launch_bounds__(kPeBlock) void k_pred_err(PeArgs a) {
   __shared__ PeInfo info[kPeTasks];
-  __shared__ uint8_t slot_task[kPeTasks * 64 / 4];   // task of each 4-lane slot
+  __shared__ uint8_t slot_task[kGroupSlots];   // task of each 4-lane slot
   __shared__ int total_lanes;
   const int t = (int)threadIdx.x, lane = t & 63;
   const int t0 = (int)blockIdx.x * kPeTasks;
@@ -151,29 +111,24 @@ __global__ __launch_bounds__(kPeBlock) void k_pred_err(PeArgs a) {
         atomicAdd(a.invalid, 1);
         a.dist[ti] = 0xFFFFFFFFu;
       } else {
-        int nl = 0, lists[2] = {0, 0};
-        if (j.flags & FME_MC_L0) lists[nl++] = 0;
-        if (j.flags & FME_MC_L1) lists[nl++] = 1;
-        if (nl == 2 && j.ref_id[0] == j.ref_id[1] && j.mv[0][0] == j.mv[1][0] && j.mv[0][1] == j.mv[1][1])
-          nl = 1;   // xCheckIdenticalMotion: same picture, same MV -> xPredInterUni(REF_PIC_LIST_0)
+        ListMotion lm[2];
+        const int nl = resolve_lists(j.flags, j.ref_id, j.mv, j.cu_x, j.cu_y, a.pics, true, lm);
         in.nl = nl;
         const PicDesc o = a.pics[j.org_id];
-        for (int k = 0; k < nl; k++) {
-          const int l = lists[k];
-          const PicDesc p = a.pics[j.ref_id[l]];
-          int mx = j.mv[l][0], my = j.mv[l][1];
-          clip_mv(mx, my, p.width, p.height, j.cu_x, j.cu_y);
-          in.ix[k] = mx >> 2;
-          in.iy[k] = my >> 2;
-          in.fx[k] = mx & 3;
-          in.fy[k] = my & 3;
-          in.ref[k] = p.luma;
-          in.rstride[k] = p.stride;
-          in.ral[k] = ((p.stride | (int)(uintptr_t)p.luma) & 3) == 0;
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+          if (k >= nl) break;
+          in.ix[k] = lm[k].lix;
+          in.iy[k] = lm[k].liy;
+          in.fx[k] = lm[k].lfx;
+          in.fy[k] = lm[k].lfy;
+          in.ref[k] = lm[k].pic.luma;
+          in.rstride[k] = lm[k].pic.stride;
+          in.ral[k] = dword_rows(lm[k].pic.luma, lm[k].pic.stride);
         }
         in.org = o.luma;
         in.ostride = o.stride;
-        in.oal = ((o.stride | (int)(uintptr_t)o.luma) & 3) == 0;
+        in.oal = dword_rows(o.luma, o.stride);
         in.pw = o.width;
         in.ph = o.height;
         in.x = j.x;
@@ -182,23 +137,12 @@ __global__ __launch_bounds__(kPeBlock) void k_pred_err(PeArgs a) {
         const int units = (j.w >> 2) * (j.h >> 2);
         in.units = units;
         const bool had = a.use_hadamard && !(j.flags & FME_PE_LOSSLESS);
-        in.mode = !had ? kPeSad : ((j.w | j.h) & 7) ? kPeHad4 : kPeHad8;
-        lanes = 4;
-        while (lanes < units && lanes < 64) lanes <<= 1;
+        in.mode = dist_mode(had, j.w, j.h);
+        lanes = group_lanes(units);
       }
     }
-    // pack the groups by size class, largest first: every start is a multiple of its group size
-    int base = 0, start = 0;
-#pragma unroll
-    for (int c = 64; c >= 4; c >>= 1) {
-      const unsigned long long m = __ballot(lanes == c);
-      if (lanes == c) start = base + c * __popcll(m & ((1ull << lane) - 1ull));
-      base += c * __popcll(m);
-    }
     in.lanes = lanes;
-    in.start = start;
-    for (int i = 0; i < (lanes >> 2); i++) slot_task[(start >> 2) + i] = (uint8_t)t;
-    if (t == 0) total_lanes = base;
+    in.start = pack_groups(lanes, lane, slot_task, total_lanes);
   }
   __syncthreads();
   const int total = total_lanes;
@@ -216,51 +160,15 @@ __global__ __launch_bounds__(kPeBlock) void k_pred_err(PeArgs a) {
       // multiple of 4), run the same iterations: the quad's cross-lane stages see all four lanes
       for (int u = li; u < units; u += G) {
         int ux, uy;
-        if (mode == kPeHad8) {   // quadrants of one 8x8 block in consecutive lanes
-          const int bxn = uxn >> 1, b = u >> 2;
-          ux = 2 * (b % bxn) + (u & 1);
-          uy = 2 * (b / bxn) + ((u >> 1) & 1);
-        } else {
-          ux = u % uxn;
-          uy = u / uxn;
-        }
+        unit_xy(u, uxn, mode == kDistHad8, ux, uy);
         const int x = in.x + 4 * ux, y = in.y + 4 * uy;
         int p[4][4], d[4][4];
         pe_predict<k10>(in, x, y, p);
         pe_diff<k10>(in, x, y, p, d);
-        uint32_t s = 0;
-        if (mode == kPeSad) {
-#pragma unroll
-          for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) s += (uint32_t)abs(d[r][c]);
-          acc += s;
-        } else {
-          had4x4(d);
-          if (mode == kPeHad4) {
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-              for (int c = 0; c < 4; c++) s += (uint32_t)abs(d[r][c]);
-            acc += (s + 1) >> 1;
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-              for (int c = 0; c < 4; c++) s += (uint32_t)abs(bfly<2>(bfly<1>(d[r][c], lane), lane));
-            s = xsum<2>(xsum<1>(s, lane), lane);   // the 8x8 block's sum of |coef|, in its four lanes
-            if ((u & 3) == 0) acc += (s + 2) >> 2;
-          }
-        }
+        acc += unit_dist(d, mode, lane, (u & 3) == 0);
       }
     }
-    // group sum (every lane of the workgroup is here; idle lanes add 0)
-    { const uint32_t v = (uint32_t)xor_lane<1>((int)acc, lane); acc += v; }
-    { const uint32_t v = (uint32_t)xor_lane<2>((int)acc, lane); acc += v; }
-    { const uint32_t v = (uint32_t)xor_lane<4>((int)acc, lane); if (G > 4) acc += v; }
-    { const uint32_t v = (uint32_t)xor_lane<8>((int)acc, lane); if (G > 8) acc += v; }
-    { const uint32_t v = (uint32_t)xor_lane<16>((int)acc, lane); if (G > 16) acc += v; }
-    { const uint32_t v = (uint32_t)xor_lane<32>((int)acc, lane); if (G > 32) acc += v; }
+    acc = group_sum(acc, G, lane);
     if (act && li == 0) a.dist[t0 + q] = acc >> (k10 ? a.bit_depth - 8 : 0);
   }
 }
@@ -268,10 +176,7 @@ __global__ __launch_bounds__(kPeBlock) void k_pred_err(PeArgs a) {
 }  // namespace
 
 hipError_t launch_pred_err(const PeArgs& a, hipStream_t s) {
-  const dim3 g((a.n + kPeTasks - 1) / kPeTasks);
-  if (a.n > 0 && a.bit_depth > 8) hipLaunchKernelGGL(k_pred_err<true>, g, dim3(kPeBlock), 0, s, a);
-  else if (a.n > 0) hipLaunchKernelGGL(k_pred_err<false>, g, dim3(kPeBlock), 0, s, a);
-  return hipGetLastError();
+  return launch_by_depth(k_pred_err<false>, k_pred_err<true>, (a.n + kPeTasks - 1) / kPeTasks, kPeBlock, a, s);
 }
 
 }  // namespace fme

@@ -37,7 +37,7 @@ using namespace mcl;
 using namespace xlane;
 
 constexpr int kSseBlock = 256;
-constexpr int kSseTasks = 64;   // consecutive tasks per workgroup, set up by its first wave
+constexpr int kSseTasks = kGroupTasks;   // consecutive tasks per workgroup, set up by its first wave
 
 // Per-task state shared by the workgroup (LDS), filled by one thread per task.
 struct SseInfo {
@@ -51,19 +51,12 @@ struct SseInfo {
 };
 
 __device__ __forceinline__ bool sse_task_valid(const SseArgs& a, const fme_sse_task& t) {
-  if (t.w < 4 || t.h < 4 || t.w > 64 || t.h > 64 || (t.w & 3) || (t.h & 3)) return false;
+  if (!pu_shape_ok(t.w, t.h)) return false;
   if (!(t.flags & (FME_MC_L0 | FME_MC_L1)) || (t.flags & ~(FME_MC_L0 | FME_MC_L1))) return false;
   if (t.org_id >= FME_MAX_PICTURES) return false;
   const PicDesc& o = a.pics[t.org_id];
   if (!o.luma || !o.cb || !o.cr || (int)t.x + t.w > o.width || (int)t.y + t.h > o.height) return false;
-#pragma unroll
-  for (int l = 0; l < 2; l++) {
-    if (!(t.flags & (1u << l))) continue;
-    if (t.ref_id[l] >= FME_MAX_PICTURES) return false;
-    const PicDesc& p = a.pics[t.ref_id[l]];
-    if (!p.luma || !p.cb || !p.cr || p.width != o.width || p.height != o.height) return false;
-  }
-  return true;
+  return refs_ok(t.flags, t.ref_id, a.pics, o.width, o.height, true);
 }
 
 // (org - pred)^2 >> ((bitDepth - 8) << 1) of one sample
@@ -74,50 +67,22 @@ __device__ __forceinline__ uint32_t sq(int org, int pred, int shift) {
   return k10 ? s >> shift : s;
 }
 
-// TComYuv::addAvg of the two lists' 14-bit values
-template <bool k10>
-__device__ __forceinline__ int add_avg(int p0, int p1) {
-  return k10 ? clamp_i((p0 + p1 + 16400) >> 5, 0, 1023) : clamp_i((p0 + p1 + 16448) >> 7, 0, 255);
-}
-
 // The SSE of the 4x4 luma unit at (x, y) (inside the original: the task was validated).
 template <bool k10>
 __device__ __forceinline__ uint32_t sse_luma(const SseInfo& in, int x, int y, int shift) {
   const bool uni = in.nl == 1;
-  int p[4][4], o[4][4];
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    if (k >= in.nl) break;
+  int p[4][4];
+  pred_lists<k10>(in.nl, [&](int k, int (&o)[4][4]) {
     const PicDesc& r = in.ref[k];
-    uint32_t hlo, hhi, vlo, vhi;
-    luma_taps(in.lfx[k], hlo, hhi);
-    luma_taps(in.lfy[k], vlo, vhi);
-    if constexpr (k10) {
-      pred10<8, 4>(Plane16{reinterpret_cast<const uint16_t*>(r.luma), r.stride, r.width, r.height}, x + in.lix[k],
-                   y + in.liy[k], hlo, hhi, vlo, vhi, uni, o);
-    } else {
-      UnitWin<8, 4> w;
-      w.load(Plane{r.luma, r.stride, r.width, r.height}, ((r.stride | (int)(uintptr_t)r.luma) & 3) == 0, x + in.lix[k],
-             y + in.liy[k]);
-      w.pred(hlo, hhi, vlo, vhi, uni, o);
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; rr++)
-#pragma unroll
-      for (int c = 0; c < 4; c++) p[rr][c] = k == 0 ? o[rr][c] : add_avg<k10>(p[rr][c], o[rr][c]);
-  }
+    luma_pred<k10>(luma_plane(r), dword_rows(r.luma, r.stride), x + in.lix[k], y + in.liy[k], in.lfx[k], in.lfy[k], uni,
+                   o);
+  }, p);
   uint32_t s = 0;
 #pragma unroll
   for (int rr = 0; rr < 4; rr++) {
-    if constexpr (k10) {
-      const gu16c* op = (const gu16c*)(reinterpret_cast<const uint16_t*>(in.org.luma) + (size_t)(y + rr) * in.org.stride + x);
+    const size_t row = (size_t)(y + rr) * in.org.stride + x;
 #pragma unroll
-      for (int c = 0; c < 4; c++) s += sq<true>((int)op[c], p[rr][c], shift);
-    } else {
-      const uint8_t* op = in.org.luma + (size_t)(y + rr) * in.org.stride + x;
-#pragma unroll
-      for (int c = 0; c < 4; c++) s += sq<false>((int)gld8(op + c), p[rr][c], 0);
-    }
+    for (int c = 0; c < 4; c++) s += sq<k10>(ld_sample<k10>(in.org.luma, row + c), p[rr][c], shift);
   }
   return s;
 }
@@ -126,49 +91,25 @@ __device__ __forceinline__ uint32_t sse_luma(const SseInfo& in, int x, int y, in
 template <bool k10>
 __device__ __forceinline__ uint32_t sse_chroma(const SseInfo& in, int comp, int x, int y, int shift) {
   const bool uni = in.nl == 1;
-  int p[2][2], o[2][2];
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    if (k >= in.nl) break;
-    if constexpr (k10) chroma_pred10(in.ref[k], comp, x + in.cix[k], y + in.ciy[k], in.cfx[k], in.cfy[k], uni, o);
-    else chroma_pred8(in.ref[k], comp, x + in.cix[k], y + in.ciy[k], in.cfx[k], in.cfy[k], uni, o);
-#pragma unroll
-    for (int rr = 0; rr < 2; rr++)
-#pragma unroll
-      for (int c = 0; c < 2; c++) p[rr][c] = k == 0 ? o[rr][c] : add_avg<k10>(p[rr][c], o[rr][c]);
-  }
+  int p[2][2];
+  pred_lists<k10>(in.nl, [&](int k, int (&o)[2][2]) {
+    chroma_pred<k10>(in.ref[k], comp, x + in.cix[k], y + in.ciy[k], in.cfx[k], in.cfy[k], uni, o);
+  }, p);
   const uint8_t* plane = comp == 1 ? in.org.cb : in.org.cr;
   uint32_t s = 0;
 #pragma unroll
   for (int rr = 0; rr < 2; rr++) {
-    if constexpr (k10) {
-      const gu16c* op = (const gu16c*)(reinterpret_cast<const uint16_t*>(plane) + (size_t)(y + rr) * in.org.cstride + x);
+    const size_t row = (size_t)(y + rr) * in.org.cstride + x;
 #pragma unroll
-      for (int c = 0; c < 2; c++) s += sq<true>((int)op[c], p[rr][c], shift);
-    } else {
-      const uint8_t* op = plane + (size_t)(y + rr) * in.org.cstride + x;
-#pragma unroll
-      for (int c = 0; c < 2; c++) s += sq<false>((int)gld8(op + c), p[rr][c], 0);
-    }
+    for (int c = 0; c < 2; c++) s += sq<k10>(ld_sample<k10>(plane, row + c), p[rr][c], shift);
   }
   return s;
-}
-
-// acc summed over the lane group of G lanes (every lane of the workgroup is here; idle lanes add 0)
-__device__ __forceinline__ uint32_t group_sum(uint32_t acc, int G, int lane) {
-  { const uint32_t v = (uint32_t)xor_lane<1>((int)acc, lane); acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<2>((int)acc, lane); acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<4>((int)acc, lane); if (G > 4) acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<8>((int)acc, lane); if (G > 8) acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<16>((int)acc, lane); if (G > 16) acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<32>((int)acc, lane); if (G > 32) acc += v; }
-  return acc;
 }
 
 template <bool k10>
 __global__ __launch_bounds__(kSseBlock) void k_pred_sse(SseArgs a) {
   __shared__ SseInfo info[kSseTasks];
-  __shared__ uint8_t slot_task[kSseTasks * 64 / 4];   // task of each 4-lane slot
+  __shared__ uint8_t slot_task[kGroupSlots];   // task of each 4-lane slot
   __shared__ int total_lanes;
   const int t = (int)threadIdx.x, lane = t & 63;
   const int t0 = (int)blockIdx.x * kSseTasks;
@@ -184,6 +125,9 @@ __global__ __launch_bounds__(kSseBlock) void k_pred_sse(SseArgs a) {
         a.sse[3 * (size_t)ti + 1] = 0xFFFFFFFFu;
         a.sse[3 * (size_t)ti + 2] = 0xFFFFFFFFu;
       } else {
+        // resolve_lists' text (fme_mc_luma.h), kept local: with ListMotion in SseInfo the 8-bit kernel
+        // allocates 169 VGPRs instead of 168 and loses its third wave per SIMD, and a local
+        // ListMotion copied into these fields goes to scratch
         int nl = ((j.flags & FME_MC_L0) ? 1 : 0) + ((j.flags & FME_MC_L1) ? 1 : 0);
         if (nl == 2 && j.ref_id[0] == j.ref_id[1] && j.mv[0][0] == j.mv[1][0] && j.mv[0][1] == j.mv[1][1])
           nl = 1;   // xCheckIdenticalMotion: same picture, same MV -> xPredInterUni(REF_PIC_LIST_0)
@@ -211,22 +155,11 @@ __global__ __launch_bounds__(kSseBlock) void k_pred_sse(SseArgs a) {
         in.uxn = j.w >> 2;
         const int units = (j.w >> 2) * (j.h >> 2);
         in.units = units;
-        lanes = 4;
-        while (lanes < units && lanes < 64) lanes <<= 1;
+        lanes = group_lanes(units);
       }
     }
-    // pack the groups by size class, largest first: every start is a multiple of its group size
-    int base = 0, start = 0;
-#pragma unroll
-    for (int c = 64; c >= 4; c >>= 1) {
-      const unsigned long long m = __ballot(lanes == c);
-      if (lanes == c) start = base + c * __popcll(m & ((1ull << lane) - 1ull));
-      base += c * __popcll(m);
-    }
     in.lanes = lanes;
-    in.start = start;
-    for (int i = 0; i < (lanes >> 2); i++) slot_task[(start >> 2) + i] = (uint8_t)t;
-    if (t == 0) total_lanes = base;
+    in.start = pack_groups(lanes, lane, slot_task, total_lanes);
   }
   __syncthreads();
   const int total = total_lanes;
@@ -264,10 +197,7 @@ __global__ __launch_bounds__(kSseBlock) void k_pred_sse(SseArgs a) {
 }  // namespace
 
 hipError_t launch_pred_sse(const SseArgs& a, hipStream_t s) {
-  const dim3 g((a.n + kSseTasks - 1) / kSseTasks);
-  if (a.n > 0 && a.bit_depth > 8) hipLaunchKernelGGL(k_pred_sse<true>, g, dim3(kSseBlock), 0, s, a);
-  else if (a.n > 0) hipLaunchKernelGGL(k_pred_sse<false>, g, dim3(kSseBlock), 0, s, a);
-  return hipGetLastError();
+  return launch_by_depth(k_pred_sse<false>, k_pred_sse<true>, (a.n + kSseTasks - 1) / kSseTasks, kSseBlock, a, s);
 }
 
 }  // namespace fme

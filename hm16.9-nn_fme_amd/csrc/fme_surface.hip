@@ -40,9 +40,8 @@ using namespace mcl;
 using namespace xlane;
 
 constexpr int kSfBlock = 256;
-constexpr int kSfTasks = 64;    // consecutive jobs per workgroup, set up by its first wave
+constexpr int kSfTasks = kGroupTasks;   // consecutive jobs per workgroup, set up by its first wave
 constexpr int kSfWords = 2 * FME_SURF_POINTS;   // words of one fme_surface
-enum { kSfSad = 0, kSfHad4 = 1, kSfHad8 = 2 };
 
 typedef uint32_t sf_u4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t sf_u2 __attribute__((ext_vector_type(2), aligned(4)));
@@ -75,20 +74,6 @@ __device__ __forceinline__ bool sf_job_valid(const SurfArgs& a, const fme_job& j
   if (j.org_id >= FME_MAX_PICTURES) return false;
   const PicDesc& o = a.pics[j.org_id];
   return o.luma && o.width == r.width && o.height == r.height && (int)j.x + j.w <= o.width && (int)j.y + j.h <= o.height;
-}
-
-// Unnormalised 2-D 4x4 Hadamard in place (rows, then columns).
-__device__ __forceinline__ void sf_had4x4(int (&d)[4][4]) {
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int a = d[r][0] + d[r][1], b = d[r][0] - d[r][1], c = d[r][2] + d[r][3], e = d[r][2] - d[r][3];
-    d[r][0] = a + c; d[r][1] = b + e; d[r][2] = a - c; d[r][3] = b - e;
-  }
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    const int a = d[0][c] + d[1][c], b = d[0][c] - d[1][c], e = d[2][c] + d[3][c], f = d[2][c] - d[3][c];
-    d[0][c] = a + e; d[1][c] = b + f; d[2][c] = a - e; d[3][c] = b - f;
-  }
 }
 
 // The unit's 12x12 window at rows and columns -4..+7 around plane position (bx, by), and the first
@@ -200,38 +185,10 @@ __device__ __forceinline__ void sf_position(const int (&t)[12][4], int fy, const
       for (int k = 0; k < 8; k++) sum += t[y + OY + k][c] * tp[k];
       d[y][c] = o[y][c] - SfWin<k10>::finish(sum);
     }
-  uint32_t s = 0, acc;
-  if (L.mode == kSfSad) {
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-#pragma unroll
-      for (int c = 0; c < 4; c++) s += (uint32_t)abs(d[r][c]);
-    acc = s;
-  } else {
-    sf_had4x4(d);
-    if (L.mode == kSfHad4) {
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) s += (uint32_t)abs(d[r][c]);
-      acc = (s + 1) >> 1;
-    } else {   // the lanes of a quad share a job and a round: the cross-lane stages see all four
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) s += (uint32_t)abs(bfly<2>(bfly<1>(d[r][c], L.lane), L.lane));
-      s = xsum<2>(xsum<1>(s, L.lane), L.lane);   // the 8x8 tile's sum of |coef|, in its four lanes
-      acc = L.lead8 ? (s + 2) >> 2 : 0u;
-    }
-  }
+  // the lanes of a quad share a job and a round: the cross-lane stages of an 8x8 tile see all four
+  uint32_t acc = unit_dist(d, L.mode, L.lane, L.lead8);
   if (!L.valid) acc = 0;
-  // group sum (wave-uniform control flow: every lane of the wave is here; idle lanes add 0)
-  { const uint32_t v = (uint32_t)xor_lane<1>((int)acc, L.lane); acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<2>((int)acc, L.lane); acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<4>((int)acc, L.lane); if (L.G > 4) acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<8>((int)acc, L.lane); if (L.G > 8) acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<16>((int)acc, L.lane); if (L.G > 16) acc += v; }
-  { const uint32_t v = (uint32_t)xor_lane<32>((int)acc, L.lane); if (L.G > 32) acc += v; }
+  acc = group_sum(acc, L.G, L.lane);   // wave-uniform control flow: every lane of the wave is here
   if (L.valid && L.store) L.row[idx] += acc;   // one writer per job: its group's first lane
 }
 
@@ -284,7 +241,7 @@ template <bool k10>
 __global__ __launch_bounds__(kSfBlock) void k_cost_surface(SurfArgs a) {
   __shared__ SfInfo info[kSfTasks];
   __shared__ __attribute__((aligned(16))) uint32_t out[kSfTasks * kSfWords];   // the jobs' fme_surface rows
-  __shared__ uint8_t slot_task[kSfTasks * 64 / 4];   // job of each 4-lane slot
+  __shared__ uint8_t slot_task[kGroupSlots];   // job of each 4-lane slot
   __shared__ int total_lanes;
   const int t = (int)threadIdx.x, lane = t & 63;
   const int t0 = (int)blockIdx.x * kSfTasks;
@@ -294,7 +251,7 @@ __global__ __launch_bounds__(kSfBlock) void k_cost_surface(SurfArgs a) {
     SfInfo& in = info[t];
     int lanes = 0;
     in.valid = 0;
-    in.mode = kSfSad;
+    in.mode = kDistSad;
     in.uxn = 1;
     in.units = 0;
     if (t < nt) {
@@ -310,7 +267,7 @@ __global__ __launch_bounds__(kSfBlock) void k_cost_surface(SurfArgs a) {
         in.valid = 1;
         in.ref = p.luma;
         in.rstride = p.stride;
-        in.ral = ((p.stride | (int)(uintptr_t)p.luma) & 3) == 0;
+        in.ral = dword_rows(p.luma, p.stride);
         in.pw = p.width;
         in.ph = p.height;
         in.key = nullptr;
@@ -323,7 +280,7 @@ __global__ __launch_bounds__(kSfBlock) void k_cost_surface(SurfArgs a) {
           const PicDesc o = a.pics[j.org_id];
           in.org = o.luma;
           in.ostride = o.stride;
-          in.oal = ((o.stride | (int)(uintptr_t)o.luma) & 3) == 0 && (j.x & 3) == 0;
+          in.oal = dword_rows(o.luma, o.stride) && (j.x & 3) == 0;
         }
         in.ml = a.mlambda[j.lambda_id];
         in.x = j.x;
@@ -337,23 +294,12 @@ __global__ __launch_bounds__(kSfBlock) void k_cost_surface(SurfArgs a) {
         in.mvpx = j.mvp_x;
         in.mvpy = j.mvp_y;
         const bool had = a.use_hadamard && !(j.flags & FME_JOB_LOSSLESS);
-        in.mode = !had ? kSfSad : ((j.w | j.h) & 7) ? kSfHad4 : kSfHad8;
-        lanes = 4;
-        while (lanes < units && lanes < 64) lanes <<= 1;
+        in.mode = dist_mode(had, j.w, j.h);
+        lanes = group_lanes(units);
       }
     }
-    // pack the groups by size class, largest first: every start is a multiple of its group size
-    int base = 0, start = 0;
-#pragma unroll
-    for (int c = 64; c >= 4; c >>= 1) {
-      const unsigned long long m = __ballot(lanes == c);
-      if (lanes == c) start = base + c * __popcll(m & ((1ull << lane) - 1ull));
-      base += c * __popcll(m);
-    }
     in.lanes = lanes;
-    in.start = start;
-    for (int i = 0; i < (lanes >> 2); i++) slot_task[(start >> 2) + i] = (uint8_t)t;
-    if (t == 0) total_lanes = base;
+    in.start = pack_groups(lanes, lane, slot_task, total_lanes);
   }
   __syncthreads();
   const int total = total_lanes;
@@ -370,14 +316,7 @@ __global__ __launch_bounds__(kSfBlock) void k_cost_surface(SurfArgs a) {
       const bool valid = u < units;
       const int mode = in.mode, uxn = max(in.uxn, 1);
       int ux, uy;
-      if (mode == kSfHad8) {   // quadrants of one 8x8 tile in consecutive lanes
-        const int bxn = max(uxn >> 1, 1), b = u >> 2;
-        ux = 2 * (b % bxn) + (u & 1);
-        uy = 2 * (b / bxn) + ((u >> 1) & 1);
-      } else {
-        ux = u % uxn;
-        uy = u / uxn;
-      }
+      unit_xy(u, uxn, mode == kDistHad8, ux, uy);
       const int x = in.x + 4 * ux, y = in.y + 4 * uy;
       SfWin<k10> win;
       win.load(in, x + in.mvx, y + in.mvy, valid);
@@ -459,10 +398,7 @@ __global__ __launch_bounds__(kSfBlock) void k_cost_surface(SurfArgs a) {
 }  // namespace
 
 hipError_t launch_cost_surface(const SurfArgs& a, hipStream_t s) {
-  const dim3 g((a.n + kSfTasks - 1) / kSfTasks);
-  if (a.n > 0 && a.bit_depth > 8) hipLaunchKernelGGL(k_cost_surface<true>, g, dim3(kSfBlock), 0, s, a);
-  else if (a.n > 0) hipLaunchKernelGGL(k_cost_surface<false>, g, dim3(kSfBlock), 0, s, a);
-  return hipGetLastError();
+  return launch_by_depth(k_cost_surface<false>, k_cost_surface<true>, (a.n + kSfTasks - 1) / kSfTasks, kSfBlock, a, s);
 }
 
 }  // namespace fme

@@ -674,36 +674,40 @@ typedef struct orc_win {
   int stride;
 } orc_win;
 
-/* TComInterpolationFilter::filterCopy (TComInterpolationFilter.cpp:94-154), bit depth 8:
- * isFirst == isLast -> copy; isFirst -> (x << 6) - 8192; else ((x + 8192 + 32) >> 6) clipped. */
-static void mc_copy(const int16_t* src, int ss, int16_t* dst, int ds, int w, int h, int first, int last) {
+/* TComInterpolationFilter::filterCopy (TComInterpolationFilter.cpp:94-154), shift = 14 - bitDepth
+ * (6 at 8 bits): isFirst == isLast -> copy; isFirst -> (x << shift) - 8192; else
+ * ((x + 8192 + (1 << (shift - 1))) >> shift) clipped. */
+static void mc_copy(const int16_t* src, int ss, int16_t* dst, int ds, int w, int h, int first, int last, int bd) {
+  const int hr = 14 - bd;
   for (int r = 0; r < h; r++)
     for (int c = 0; c < w; c++) {
       int v = src[r * ss + c];
       if (first == last) {
       } else if (first) {
-        v = (v << 6) - 8192;
+        v = (v << hr) - 8192;
       } else {
-        v = clampi((v + 8192 + 32) >> 6, 0, 255);
+        v = clampi((v + 8192 + (1 << (hr - 1))) >> hr, 0, (1 << bd) - 1);
       }
       dst[r * ds + c] = (int16_t)v;
     }
 }
 
-/* filter<N, isVertical, isFirst, isLast> (TComInterpolationFilter.cpp:172-257), bit depth 8:
- * headRoom 6; isLast: shift 6 (+6 when !isFirst), offset 1 << (shift-1) (+ 8192 << 6 when
- * !isFirst), clip; else shift 6 - 6 (isFirst) or 6, offset -8192 (isFirst) or 0. */
+/* filter<N, isVertical, isFirst, isLast> (TComInterpolationFilter.cpp:172-257): headRoom
+ * 14 - bitDepth (6 at 8 bits); isLast: shift 6 (+ headRoom when !isFirst), offset 1 << (shift-1)
+ * (+ 8192 << 6 when !isFirst), clip; else shift 6 - headRoom (isFirst) or 6, offset
+ * -8192 << shift (isFirst) or 0. */
 static void mc_filter(int ntaps, const int* coef, int vert, int first, int last, const int16_t* src, int ss,
-                      int16_t* dst, int ds, int w, int h) {
+                      int16_t* dst, int ds, int w, int h, int bd) {
+  const int hr = 14 - bd;
   const int cstride = vert ? ss : 1;
   const int16_t* s0 = src - (ntaps / 2 - 1) * cstride;
   int shift = 6, offset;
   if (last) {
-    shift += first ? 0 : 6;
+    shift += first ? 0 : hr;
     offset = 1 << (shift - 1);
     offset += first ? 0 : 8192 << 6;
   } else {
-    shift -= first ? 6 : 0;
+    shift -= first ? hr : 0;
     offset = first ? -8192 * (1 << shift) : 0;   /* -8192 << shift (UB in C) */
   }
   for (int r = 0; r < h; r++)
@@ -711,7 +715,7 @@ static void mc_filter(int ntaps, const int* coef, int vert, int first, int last,
       int sum = 0;
       for (int k = 0; k < ntaps; k++) sum += s0[r * ss + c + k * cstride] * coef[k];
       int v = (sum + offset) >> shift;
-      if (last) v = clampi(v, 0, 255);
+      if (last) v = clampi(v, 0, (1 << bd) - 1);
       dst[r * ds + c] = (int16_t)v;
     }
 }
@@ -725,9 +729,10 @@ static void mc_clip_mv(int* mx, int* my, int pic_w, int pic_h, int cu_x, int cu_
 }
 
 /* xPredInterBlk (TComPrediction.cpp:616-668) for one component: W x H at (x0,y0) of a plane
- * (pw x ph), MV in units of 1 << shift samples; bi keeps 14-bit output. */
+ * (pw x ph), MV in units of 1 << shift samples; bi keeps 14-bit output.  bd > 8: the plane holds
+ * uint16 samples (stride in samples). */
 static void mc_pred_blk(const uint8_t* plane, int stride, int pw, int ph, int chroma, int x0, int y0, int w, int h,
-                        int mx, int my, int bi, int16_t* dst, int ds) {
+                        int mx, int my, int bi, int16_t* dst, int ds, int bd) {
   const int ntaps = chroma ? 4 : 8, sh = chroma ? 3 : 2;
   const int ix = mx >> sh, iy = my >> sh, fx = mx & ((1 << sh) - 1), fy = my & ((1 << sh) - 1);
   /* padded window: rows -ntaps/2+1 .. h+ntaps/2, cols likewise, around the displaced block */
@@ -737,7 +742,8 @@ static void mc_pred_blk(const uint8_t* plane, int stride, int pw, int ph, int ch
   for (int r = 0; r < wh; r++)
     for (int c = 0; c < ww; c++) {
       const int yy = clampi(y0 + iy + r - pad, 0, ph - 1), xx = clampi(x0 + ix + c - pad, 0, pw - 1);
-      win[r * ww + c] = plane[(size_t)yy * stride + xx];
+      win[r * ww + c] = bd > 8 ? (int16_t)((const uint16_t*)plane)[(size_t)yy * stride + xx]
+                               : plane[(size_t)yy * stride + xx];
     }
   const int16_t* ref = win + pad * ww + pad;
   int ch[8], cv[8];
@@ -746,13 +752,13 @@ static void mc_pred_blk(const uint8_t* plane, int stride, int pw, int ph, int ch
     cv[k] = chroma ? kChroma[fy][k] : kLuma[fy][k];
   }
   if (fy == 0) {         /* filterHor(frac = fx, isLast = !bi); fx == 0 -> filterCopy */
-    if (fx == 0) mc_copy(ref, ww, dst, ds, w, h, 1, !bi);
-    else mc_filter(ntaps, ch, 0, 1, !bi, ref, ww, dst, ds, w, h);
+    if (fx == 0) mc_copy(ref, ww, dst, ds, w, h, 1, !bi, bd);
+    else mc_filter(ntaps, ch, 0, 1, !bi, ref, ww, dst, ds, w, h, bd);
   } else if (fx == 0) {  /* filterVer(frac = fy, isFirst = true, isLast = !bi) */
-    mc_filter(ntaps, cv, 1, 1, !bi, ref, ww, dst, ds, w, h);
+    mc_filter(ntaps, cv, 1, 1, !bi, ref, ww, dst, ds, w, h, bd);
   } else {               /* filterHor over h + ntaps - 1 rows, then filterVer(isFirst = false) */
-    mc_filter(ntaps, ch, 0, 1, 0, ref - (ntaps / 2 - 1) * ww, ww, tmp, w, w, h + ntaps - 1);
-    mc_filter(ntaps, cv, 1, 0, !bi, tmp + (ntaps / 2 - 1) * w, w, dst, ds, w, h);
+    mc_filter(ntaps, ch, 0, 1, 0, ref - (ntaps / 2 - 1) * ww, ww, tmp, w, w, h + ntaps - 1, bd);
+    mc_filter(ntaps, cv, 1, 0, !bi, tmp + (ntaps / 2 - 1) * w, w, dst, ds, w, h, bd);
   }
   free(win);
   free(tmp);
@@ -780,8 +786,11 @@ static int wp_sample(const int (*wp)[FME_MAX_PICTURES][3][3], const fme_mc_job* 
   return clampi((((p0 + 8192) + (1 << (shift_num - 1))) >> shift_num) + a[1], 0, 255);
 }
 
+/* bd > 8: the pictures and y / cb / cr hold uint16 samples (strides in samples); weighted
+ * prediction is restated at 8 bits only. */
 static int mc_run_jobs(const orc_yuv* pics, const fme_mc_job* jobs, int n, uint8_t* y, int ys, uint8_t* cb,
-                       uint8_t* cr, int cs, int width, int height, const int (*wp)[FME_MAX_PICTURES][3][3]) {
+                       uint8_t* cr, int cs, int width, int height, const int (*wp)[FME_MAX_PICTURES][3][3], int bd) {
+  const int avg_shift = 15 - bd, avg_off = (1 << (avg_shift - 1)) + 2 * 8192;
   for (int i = 0; i < n; i++) {
     const fme_mc_job* j = &jobs[i];
     const int wpf = wp && (j->flags & FME_MC_WP);
@@ -809,17 +818,19 @@ static int mc_run_jobs(const orc_yuv* pics, const fme_mc_job* jobs, int n, uint8
         mc_clip_mv(&mx, &my, p->width, p->height, j->cu_x, j->cu_y);
         const uint8_t* plane = comp == 0 ? p->y : (comp == 1 ? p->cb : p->cr);
         mc_pred_blk(plane, comp ? p->c_stride : p->y_stride, p->width >> c, p->height >> c, c, x0, y0, w, h, mx, my,
-                    nl == 2 || wpf, pred[k], w);
+                    nl == 2 || wpf, pred[k], w, bd);
       }
       uint8_t* out = comp == 0 ? y : (comp == 1 ? cb : cr);
       const int os = comp ? cs : ys;
       for (int r = 0; r < h; r++)
         for (int q = 0; q < w; q++) {
           int v = pred[0][r * w + q];
-          /* TComYuv::addAvg (TComYuv.cpp:354-415): shiftNum 7, offset 64 + 2 * 8192 */
+          /* TComYuv::addAvg (TComYuv.cpp:354-415): shiftNum 15 - bitDepth (7 at 8 bits), offset
+           * 1 << (shiftNum - 1) + 2 * 8192 (16448 at 8 bits) */
           if (wpf) v = wp_sample(wp, j, lists, nl, comp, pred[0][r * w + q], nl == 2 ? pred[1][r * w + q] : 0);
-          else if (nl == 2) v = clampi((pred[0][r * w + q] + pred[1][r * w + q] + 16448) >> 7, 0, 255);
-          out[(size_t)(y0 + r) * os + x0 + q] = (uint8_t)v;
+          else if (nl == 2) v = clampi((pred[0][r * w + q] + pred[1][r * w + q] + avg_off) >> avg_shift, 0, (1 << bd) - 1);
+          if (bd > 8) ((uint16_t*)out)[(size_t)(y0 + r) * os + x0 + q] = (uint16_t)v;
+          else out[(size_t)(y0 + r) * os + x0 + q] = (uint8_t)v;
         }
     }
   }
@@ -828,13 +839,20 @@ static int mc_run_jobs(const orc_yuv* pics, const fme_mc_job* jobs, int n, uint8
 
 int orc_mc(const orc_yuv* pics, const fme_mc_job* jobs, int n, uint8_t* y, int ys, uint8_t* cb, uint8_t* cr,
            int cs, int width, int height) {
-  return mc_run_jobs(pics, jobs, n, y, ys, cb, cr, cs, width, height, NULL);
+  return mc_run_jobs(pics, jobs, n, y, ys, cb, cr, cs, width, height, NULL, 8);
+}
+
+/* orc_mc at bit depth bd (10): the pictures' planes and y / cb / cr hold uint16 samples. */
+int orc_mc16(const orc_yuv* pics, const fme_mc_job* jobs, int n, uint16_t* y, int ys, uint16_t* cb, uint16_t* cr,
+             int cs, int width, int height, int bd) {
+  if (bd <= 8 || bd > 12) return -1;
+  return mc_run_jobs(pics, jobs, n, (uint8_t*)y, ys, (uint8_t*)cb, (uint8_t*)cr, cs, width, height, NULL, bd);
 }
 
 /* orc_mc with FME_MC_WP jobs weighted by wp9 = [2][FME_MAX_PICTURES][3 components][3] ints. */
 int orc_mc_wp(const orc_yuv* pics, const fme_mc_job* jobs, int n, const int* wp9, uint8_t* y, int ys, uint8_t* cb,
               uint8_t* cr, int cs, int width, int height) {
-  return mc_run_jobs(pics, jobs, n, y, ys, cb, cr, cs, width, height, (const int (*)[FME_MAX_PICTURES][3][3])wp9);
+  return mc_run_jobs(pics, jobs, n, y, ys, cb, cr, cs, width, height, (const int (*)[FME_MAX_PICTURES][3][3])wp9, 8);
 }
 
 /* =====================================================================================
@@ -1257,7 +1275,7 @@ static void pi_pred_uni(const orc_ctx* ctx, const pi_pu* g, int ref_id, int mx, 
     orc_pred_block(ref, g->x, g->y, g->w, g->h, mx, my, pred);
     return;
   }
-  mc_pred_blk(ref->luma, ref->stride, ref->width, ref->height, 0, g->x, g->y, g->w, g->h, mx, my, 0, pred, g->w);
+  mc_pred_blk(ref->luma, ref->stride, ref->width, ref->height, 0, g->x, g->y, g->w, g->h, mx, my, 0, pred, g->w, 8);
 }
 
 static uint32_t pi_tmpl(const orc_ctx* ctx, const pi_pu* g, int ref_id, int mx, int my, int m, int16_t* pred) {

@@ -151,6 +151,10 @@ typedef struct orc_yuv {
  * pics[ref_id] are the reference pictures.  Returns 0, or -1-i for an invalid job i. */
 int orc_mc(const orc_yuv* pics, const fme_mc_job* jobs, int n, uint8_t* y, int y_stride,
            uint8_t* cb, uint8_t* cr, int c_stride, int width, int height);
+/* The same at bit depth bd (9..12): the pictures' planes (cast to uint8_t*) and y / cb / cr hold
+ * uint16 samples, strides in samples. */
+int orc_mc16(const orc_yuv* pics, const fme_mc_job* jobs, int n, uint16_t* y, int y_stride,
+             uint16_t* cb, uint16_t* cr, int c_stride, int width, int height, int bd);
 /* Motion compensation with explicit weighted prediction for the jobs with FME_MC_WP (8-bit):
  * wp9 = int[2][FME_MAX_PICTURES][3][3], per list, picture and component {iWeight, iOffset,
  * uiLog2WeightDenom}. */

@@ -263,15 +263,18 @@ class Oracle:
         return int(self.lib.orc_template_cost(self.ctx, _ptr(r), int(k), int(m)))
 
     def mc(self, pics, mc_jobs, y, cb, cr, wp=None):
-        """orc_mc: pics = {id: (Y, Cb, Cr)} reference pictures; predicts into y/cb/cr in place.
-        wp: [2][refs][3][3] (iWeight, iOffset, uiLog2WeightDenom) for the FME_MC_WP jobs (orc_mc_wp)."""
+        """orc_mc: pics = {id: (Y, Cb, Cr)} reference pictures; predicts into y/cb/cr in place (uint8
+        planes, or uint16 at a bit depth above 8: orc_mc16).
+        wp: [2][refs][3][3] (iWeight, iOffset, uiLog2WeightDenom) for the FME_MC_WP jobs (orc_mc_wp, 8-bit)."""
+        dt = np.uint16 if self.bit_depth > 8 and wp is None else np.uint8
+        assert y.dtype == dt and cb.dtype == dt and cr.dtype == dt
         class Yuv(C.Structure):
             _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_stride", C.c_int),
                         ("c_stride", C.c_int), ("width", C.c_int), ("height", C.c_int)]
         arr = (Yuv * 64)()
         keep = []
         for pid, (py, pcb, pcr) in pics.items():
-            py, pcb, pcr = (np.ascontiguousarray(a, dtype=np.uint8) for a in (py, pcb, pcr))
+            py, pcb, pcr = (np.ascontiguousarray(a, dtype=dt) for a in (py, pcb, pcr))
             keep += [py, pcb, pcr]
             arr[pid] = Yuv(py.ctypes.data, pcb.ctypes.data, pcr.ctypes.data, py.shape[1], pcb.shape[1],
                            py.shape[1], py.shape[0])
@@ -285,6 +288,10 @@ class Oracle:
             self.lib.orc_mc_wp.argtypes = [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int]
             rc = self.lib.orc_mc_wp(C.cast(arr, C.c_void_p), _ptr(jobs), len(jobs), _ptr(t), _ptr(y), y.shape[1],
                                     _ptr(cb), _ptr(cr), cb.shape[1], w, h)
+        elif dt == np.uint16:
+            self.lib.orc_mc16.argtypes = [_P, _P, C.c_int, _P, C.c_int, _P, _P] + [C.c_int] * 4
+            rc = self.lib.orc_mc16(C.cast(arr, C.c_void_p), _ptr(jobs), len(jobs), _ptr(y), y.shape[1], _ptr(cb),
+                                   _ptr(cr), cb.shape[1], w, h, self.bit_depth)
         else:
             rc = self.lib.orc_mc(C.cast(arr, C.c_void_p), _ptr(jobs), len(jobs), _ptr(y), y.shape[1], _ptr(cb), _ptr(cr),
                                  cb.shape[1], w, h)

@@ -36,7 +36,7 @@ def test_mc_golden(case):
 @pytest.mark.parametrize("case", mc10_golden_cases())
 def test_mc10_golden(case):
     """Bit depth 10 (main10): uint16 planes through fme_motion_compensate against the reference's
-    own filters and addAvg at bitDepth 10 (k_mc10)."""
+    own filters and addAvg at bitDepth 10 (k_mc<true>)."""
     from nnfme.runtime import FmeContext
     g = load_golden(case)
     pics, jobs, planes = mc_inputs(g)
@@ -117,6 +117,100 @@ def test_mc_device_1080p_matches_oracle():
     ctx.motion_compensate_device(dj.data_ptr(), len(jobs), dy.data_ptr(), W, dcb.data_ptr(), dcr.data_ptr(), W // 2,
                                  W, H, s)
     _same((dy.cpu().numpy(), dcb.cpu().numpy(), dcr.cpu().numpy()), exp, "1080p rerun")
+
+
+_SENTINEL = 0xA5   # pre-filled into the output planes: a sample no job owns must keep it
+
+
+def _small_frame(bit_depth):
+    """A 72x40 picture (not a multiple of the CTU) with three references, its partition (half
+    bi-pred, a fifth of those with identical motion, MVs up to +-200 pel so clipMv and the edge
+    replication act) and the oracle's planes for the first n jobs."""
+    from oracle import Oracle
+    W, H = 72, 40
+    rng = np.random.default_rng(91)
+    pics = {}
+    for k in range(3):
+        cb, cr = synth.synth_chroma(W, H, k)
+        if bit_depth == 8:
+            pics[k] = (synth.synth_luma(W, H, k), cb, cr)
+        else:
+            lo = rng.integers(0, 4, size=(2,) + cb.shape, dtype=np.uint16)
+            pics[k] = (synth.synth_luma_hbd(W, H, k, bit_depth=10), (cb.astype(np.uint16) << 2) | lo[0],
+                       (cr.astype(np.uint16) << 2) | lo[1])
+    jobs = synth.make_mc_partition(rng, W, H, [0, 1, 2], bi_frac=0.5, mv_amp=200, identical_frac=0.2)
+    dt = np.uint16 if bit_depth > 8 else np.uint8
+    orc = Oracle(bit_depth=bit_depth)
+
+    def expect(n):
+        exp = tuple(np.full(s, _SENTINEL, dt) for s in ((H, W), (H // 2, W // 2), (H // 2, W // 2)))
+        orc.mc(pics, jobs[:n], *exp)
+        return exp
+
+    return W, H, pics, jobs, expect
+
+
+_small_frames = {}
+
+
+def _small(bit_depth):
+    if bit_depth not in _small_frames:
+        _small_frames[bit_depth] = _small_frame(bit_depth)
+    return _small_frames[bit_depth]
+
+
+def _mc_device(ctx, jobs, W, H, y_stride, c_stride, tdt):
+    """Device-resident jobs into sentinel-filled planes of the given strides; returns the planes."""
+    import torch
+    dev = torch.device("cuda", 0)
+    dj = torch.from_numpy(jobs.view(np.uint8).copy()).to(dev)
+    dy = torch.full((H, y_stride), _SENTINEL, dtype=tdt, device=dev)
+    dcb = torch.full((H // 2, c_stride), _SENTINEL, dtype=tdt, device=dev)
+    dcr = torch.full((H // 2, c_stride), _SENTINEL, dtype=tdt, device=dev)
+    ctx.motion_compensate_device(dj.data_ptr(), len(jobs), dy.data_ptr(), y_stride, dcb.data_ptr(), dcr.data_ptr(),
+                                 c_stride, W, H, torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    return dy.cpu().numpy(), dcb.cpu().numpy(), dcr.cpu().numpy()
+
+
+@pytest.mark.parametrize("n", [1, 7, 8, 9, 17])
+@pytest.mark.parametrize("bit_depth", [8, 10])
+def test_mc_workgroup_boundaries(bit_depth, n):
+    """k_mc's workgroup tiling (kMcJobs = 8 jobs per workgroup): one job, a part group, exactly one
+    group, one over, two groups plus one.  Every sample equals the oracle's on the same n jobs, so
+    every sample outside the n PUs still holds the sentinel; no job is rejected."""
+    import torch
+    from nnfme.runtime import FmeContext
+    W, H, pics, jobs, expect = _small(bit_depth)
+    assert len(jobs) >= 17
+    ctx = FmeContext(nn_mode=0, bit_depth=bit_depth)
+    for k, p in pics.items():
+        ctx.set_picture_yuv(k, *p)
+    tdt, ndt = (torch.uint8, np.uint8) if bit_depth == 8 else (torch.int16, np.uint16)
+    got = tuple(p.view(ndt) for p in _mc_device(ctx, jobs[:n], W, H, W, W // 2, tdt))
+    assert ctx.mc_invalid_count() == 0
+    exp = expect(n)
+    _same(got, exp, f"{bit_depth}-bit, {n} jobs")
+    own = np.zeros((H, W), bool)
+    for j in jobs[:n]:
+        own[j["y"]:j["y"] + j["h"], j["x"]:j["x"] + j["w"]] = True
+    assert (got[0][~own] == _SENTINEL).all()
+    assert (got[1][~own[::2, ::2]] == _SENTINEL).all() and (got[2][~own[::2, ::2]] == _SENTINEL).all()
+
+
+def test_mc_unaligned_output_planes():
+    """8 bits, device form, output strides W + 2 (luma, no multiple of 4) and W/2 + 1 (chroma, odd):
+    store_row takes its per-byte path.  The W x H views equal the oracle's contiguous planes and the
+    padding columns keep the sentinel."""
+    import torch
+    W, H, pics, jobs, expect = _small(8)
+    ctx = _ctx(pics)
+    got = _mc_device(ctx, jobs, W, H, W + 2, W // 2 + 1, torch.uint8)
+    assert ctx.mc_invalid_count() == 0
+    exp = expect(len(jobs))
+    _same((got[0][:, :W], got[1][:, :W // 2], got[2][:, :W // 2]), exp, "unaligned planes")
+    for p, w in zip(got, (W, W // 2, W // 2)):
+        assert (p[:, w:] == _SENTINEL).all()
 
 
 def test_mc_invalid_jobs():

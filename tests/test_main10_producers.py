@@ -105,7 +105,7 @@ def test_main10_oracle_bi_key_matches_reference_harness():
 # ---- GPU parity (through the C ABI) ---------------------------------------------------------------
 @pytest.mark.gpu
 def test_main10_gpu_template_costs_match_reference_harness():
-    """fme_template_costs on a 10-bit context (k_amvp_sad10) against oracle/_ref at bitDepth 10."""
+    """fme_template_costs on a 10-bit context (k_amvp_sad<true>) against oracle/_ref at bitDepth 10."""
     from nnfme.runtime import FmeContext
     pics = _pics10()
     ref = _reference10(pics)
@@ -162,7 +162,7 @@ def test_main10_pred_inter_p_matches_oracle():
 @pytest.mark.parametrize("fen", [1, 0])
 def test_main10_pred_inter_b_matches_oracle(fen):
     """A 10-bit B request stream (2 + 2 references, one shared; FEN 1: one bi-pred iteration, FEN 0:
-    four) on the GPU against the oracle: the bi-pred keys (k_bi_key10), their integer searches and
+    four) on the GPU against the oracle: the bi-pred keys (k_bi_key<true>), their integer searches and
     refinements, the uni / bi decision."""
     from nnfme import weights
     from nnfme.runtime import FmeContext

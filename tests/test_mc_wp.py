@@ -129,7 +129,7 @@ def test_gpu_mcwp_matches_golden(case):
 
 
 def test_unit_weight_branch_identity():
-    """k_mc / k_mc10 use one uni-pred formula, ((w (p + 8192) + 2^(s-1)) >> s) + o with s = d + shiftNum,
+    """k_mc<k10> uses one uni-pred formula, ((w (p + 8192) + 2^(s-1)) >> s) + o with s = d + shiftNum,
     where addWeightUni switches to noWeightUnidir ((p + 8192 + 2^(n-1)) >> n) + o when w == 1 << d
     (TComWeightPrediction.cpp:170-238): the two agree for every 14-bit value, denominator and bit depth."""
     p = np.arange(-8192, 16384 + 1, dtype=np.int64)

@@ -143,6 +143,16 @@ def test_mc10_golden_is_the_reference(case):
         assert got.dtype == np.uint16 and np.array_equal(got, exp), f"{case} {comp}"
 
 
+@pytest.mark.parametrize("case", mc10_golden_cases())
+def test_mc10_oracle_matches_golden(case):
+    """orc_mc16 (the plain-C restatement at bitDepth 10) against the reference's motion compensation."""
+    g = load_golden(case)
+    pics, jobs, (y, cb, cr) = mc_inputs(g)
+    Oracle(bit_depth=10).mc(pics, jobs, y, cb, cr)
+    for got, exp, comp in ((y, g["pred_y"], "Y"), (cb, g["pred_cb"], "Cb"), (cr, g["pred_cr"], "Cr")):
+        assert got.dtype == np.uint16 and np.array_equal(got, exp), f"{case} {comp}: {int((got != exp).sum())} differ"
+
+
 def test_mc10_goldens_cover_bi_clip_and_range():
     bi = uni = 0
     for case in mc10_golden_cases():
