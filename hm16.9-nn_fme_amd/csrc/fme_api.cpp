@@ -23,10 +23,10 @@ namespace {
 thread_local std::string g_last_error = "";
 }  // namespace
 
-// counts buffer: two counter blocks of kCountWords (fme_device.h: 25 class counts (+ invalid), 24
-// scatter cursors, 8 lane tile-queue heads, the keyed-job count), both zeroed at allocation.  A
-// refinement batch counts in block counts_cur and its k_scatter zeroes the other one, which the
-// next batch uses: no fill dispatch per batch.  Whatever else touches the blocks (the integer
+// counts buffer: two counter blocks of kCountWords (fme_device.h: three 128-byte lines with the
+// integer search's class histogram and k_front's done ticket, the 24 scatter cursors with k_front's
+// invalid and keyed counts, and the 8 lane tile-queue heads), both zeroed at allocation.  A refinement batch counts in block counts_cur and its k_front (the workgroup that
+// finishes last) zeroes the other one, which the next batch uses: no fill dispatch per batch.  Whatever else touches the blocks (the integer
 // search, a batch whose launches failed midway) sets counts_dirty, and the next batch starts with
 // one hipMemsetAsync of both blocks (use_counts).
 
@@ -80,8 +80,9 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
   if (cfg->max_jobs > 0) {
     const size_t n = (size_t)cfg->max_jobs;
     const size_t nb = (n + kJobsPerScanBlock - 1) / kJobsPerScanBlock;
+    if (n * kNumClasses > (size_t)INT32_MAX) return fail(FME_E_INVALID, "fme_create: max_jobs %d", cfg->max_jobs);
     HIP_TRY(c->cls.reserve(n));
-    HIP_TRY(c->perm.reserve(n));
+    HIP_TRY(c->perm.reserve(n * kNumClasses));   // one region of n jobs per class (k_front)
     HIP_TRY(c->blk_agg.reserve(nb * 9));
     HIP_TRY(c->blk_prefix.reserve(nb * 9));
   }
@@ -433,25 +434,29 @@ int fme_nn_copy_state_device(fme_ctx* c, uint32_t* d_out12, void* stream) {
 
 }  // extern "C"
 
+// perm holds one region per PU class, each as long as the context's job capacity (k_front writes
+// class c's jobs from c * capacity on, whatever the batch's class totals turn out to be): 96 bytes
+// per job of capacity, 83 MB for a 1080p frame's 862,920 jobs.
 static int ensure_work(fme_ctx* c, int n) {
   const size_t nb = ((size_t)n + kJobsPerScanBlock - 1) / kJobsPerScanBlock;
+  if ((size_t)n * kNumClasses > (size_t)INT32_MAX) return fail(FME_E_INVALID, "%d jobs in one batch", n);
   HIP_TRY(c->cls.reserve(n));
-  HIP_TRY(c->perm.reserve(n));
+  HIP_TRY(c->perm.reserve((size_t)n * kNumClasses));
   HIP_TRY(c->blk_agg.reserve(nb * 9));
   HIP_TRY(c->blk_prefix.reserve(nb * 9));
   HIP_TRY(c->koff.reserve(n));
   return FME_OK;
 }
 
-// Before a batch's k_classify: the counter block it counts in is zero.  In steady state the
-// previous batch's k_scatter left it so; otherwise both blocks are filled here.  The blocks stay
+// Before a batch's k_front: the counter block it counts in is zero.  In steady state the
+// previous batch's k_front left it so; otherwise both blocks are filled here.  The blocks stay
 // marked dirty until the caller has enqueued every launch of the batch (counts_done).
 static int counts_begin(fme_ctx* c, hipStream_t s) {
   if (c->counts_dirty) HIP_TRY(hipMemsetAsync(c->counts.p, 0, 2 * kCountWords * sizeof(int32_t), s));
   c->counts_dirty = true;
   return FME_OK;
 }
-// A refinement batch fully enqueued: its k_scatter zeroes the other block, which the next batch uses.
+// A refinement batch fully enqueued: its k_front zeroes the other block, which the next batch uses.
 static void counts_done(fme_ctx* c) {
   c->counts_cur ^= 1;
   c->counts_dirty = false;
@@ -461,11 +466,12 @@ static WorkBufs work_bufs(fme_ctx* c) {
   WorkBufs w{};
   w.cls = c->cls.p;
   w.perm = c->perm.p;
+  w.perm_cap = (int32_t)(c->perm.cap / kNumClasses);
   w.koff = c->koff.p;
   w.counts = c->counts.p + c->counts_cur * kCountWords;
   w.counts_next = c->counts.p + (c->counts_cur ^ 1) * kCountWords;
-  w.cursor = w.counts + kNumClasses + 1;
-  w.tile_ctr = w.counts + 2 * kNumClasses + 1;
+  w.cursor = w.counts + kCursorWord;
+  w.tile_ctr = w.counts + kTileCtrWord;
   w.blk_agg = c->blk_agg.p;
   w.blk_prefix = c->blk_prefix.p;
   w.nn_state = c->nn_state.p;
@@ -540,8 +546,8 @@ static int harvest_events(fme_ctx* c, bool wait_all) {
       HIP_TRY(q);
     }
     float* ms = c->last_ms;
-    HIP_TRY(hipEventElapsedTime(&ms[0], e[0], e[1]));
-    HIP_TRY(hipEventElapsedTime(&ms[1], e[1], e[3]));   // the scatter, which builds the schedule
+    HIP_TRY(hipEventElapsedTime(&ms[0], e[0], e[3]));   // k_front: classify, scatter and schedule in one pass
+    ms[1] = 0.f;                                        // (the scatter's own launch, until k_front)
     HIP_TRY(hipEventElapsedTime(&ms[2], e[3], e[5]));
     HIP_TRY(hipEventElapsedTime(&ms[3], e[5], e[6]));
     HIP_TRY(hipEventElapsedTime(&ms[4], e[0], e[6]));
@@ -555,11 +561,11 @@ static int harvest_events(fme_ctx* c, bool wait_all) {
   return FME_OK;
 }
 
-// One batch: classify -> schedule (device) -> scatter -> search (lane kernels on three streams,
-// cooperative AMP kernels beside them) -> NN + tail, all enqueued without waiting for the device.
+// One batch: front end (classify, scatter and schedule in one kernel) -> search -> NN + tail, all
+// enqueued without waiting for the device.
 // Device validation covers what the host cannot see for device-resident jobs: a job with an
 // unknown PU shape, an unset picture / lambda slot or a key block outside the key buffer makes
-// k_scatter mark the batch rejected; every later kernel then skips its work.
+// k_front mark the batch rejected; every later kernel then skips its work.
 // d_jobs null: the batch is d_pjobs / d_key_base (fme_job_packed rows, read in place by every kernel).
 int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_result* d_mv, int n,
                       hipStream_t s, const fme_job_packed* d_pjobs, const int32_t* d_key_base) {
@@ -599,9 +605,7 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
     HIP_TRY(hipEventRecord(ev[0], s));
   }
   FME_TRY(counts_begin(c, s));
-  HIP_TRY(launch_classify(a, w, s));
-  if (prof) HIP_TRY(hipEventRecord(ev[1], s));
-  HIP_TRY(launch_scatter(a, w, c->sched_p, s));
+  HIP_TRY(launch_front(a, w, c->sched_p, s));
   if (prof) HIP_TRY(hipEventRecord(ev[3], s));
   if (c->ev_search) HIP_TRY(hipEventRecord(c->ev_search, s));
   // the lane kernel: every PU shape, one launch on the batch stream (8-bit); the pixel kernel at
@@ -914,6 +918,25 @@ int fme_refine_status(fme_ctx* c) {
   int32_t v = 0;
   HIP_TRY(hipMemcpy(&v, &c->d_sched.p->invalid, sizeof(v), hipMemcpyDeviceToHost));
   return v;
+}
+
+// Debugging aid for the tests of the front end (not declared in include/fme.h): what the last
+// refinement batch's k_front left, read after waiting for the batch.  perm_out (may be null): the
+// first perm_words words of perm; sched_out (may be null): the first sched_words int32 words of the
+// Schedule (prefix[25], class_off[24], class_cnt[24], xq[8][25], invalid); *cap_out: the distance
+// between two class regions of perm, in jobs.
+int fme_debug_front(fme_ctx* c, int32_t* perm_out, long long perm_words, int32_t* sched_out, int sched_words,
+                    int32_t* cap_out) {
+  if (!c || !c->batch_issued) return fail(FME_E_STATE, "fme_debug_front: no batch issued");
+  if (perm_words < 0 || (size_t)perm_words > c->perm.cap || sched_words < 0 ||
+      (size_t)sched_words * sizeof(int32_t) > sizeof(Schedule))
+    return fail(FME_E_INVALID, "fme_debug_front: length");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->ev_done));
+  if (perm_out && perm_words) HIP_TRY(hipMemcpy(perm_out, c->perm.p, (size_t)perm_words * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (sched_out && sched_words) HIP_TRY(hipMemcpy(sched_out, c->d_sched.p, (size_t)sched_words * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (cap_out) *cap_out = (int32_t)(c->perm.cap / kNumClasses);
+  return FME_OK;
 }
 
 // ---- integer motion estimation (xTZSearch / xPatternSearch) -----------------------------------

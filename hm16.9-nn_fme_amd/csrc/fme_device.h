@@ -35,11 +35,21 @@ __host__ __device__ __forceinline__ constexpr int lane_class_at(int pos) {
 }
 constexpr int kBlock = 256;          // threads per workgroup (4 wavefronts)
 constexpr int kJobsPerScanBlock = 1024;  // classify / NN kernels: 4 jobs per thread
-constexpr int kKeyedWord = 60;           // counts[]: jobs that read a key block (k_classify)
-// One counter block: 25 class counts (+ invalid), 24 scatter cursors, 8 lane tile-queue heads, the
-// keyed-job count; padded to 64 words (256 B).  A context holds two, used by alternate batches.
-constexpr int kCountWords = 64;
-static_assert(2 * kNumClasses + 1 + 8 <= kKeyedWord && kKeyedWord < kCountWords, "counter block");
+// One counter block, three 128-byte lines; a context holds two, used by alternate batches.
+//   line 0: the integer search's class histogram (k_classify: 24 counts, [24] invalid jobs), its
+//           keyed-job count, and k_front's done ticket
+//   line 1: the 24 scatter cursors, then k_front's invalid and keyed counts: what a k_front
+//           workgroup adds to with its one atomic instruction
+//   line 2: the lane kernels' 8 tile-queue heads
+// k_front's two atomic instructions per workgroup (cursors, ticket) go to two lines, and the
+// cursors' instruction to one line only (DESIGN.md §5 "One-pass front end").
+constexpr int kKeyedWord = 25;           // counts[]: jobs that read a key block (k_classify)
+constexpr int kTicketWord = 28;          // counts[]: k_front's workgroups that are done (the last one builds the schedule)
+constexpr int kCursorWord = 32;          // counts[]: WorkBufs::cursor; [kNumClasses], [kNumClasses + 1]: k_front's invalid / keyed jobs
+constexpr int kTileCtrWord = 64;
+constexpr int kCountWords = 96;
+static_assert(kNumClasses < kKeyedWord && kKeyedWord < kTicketWord && kTicketWord < 32 && kCursorWord + kNumClasses + 2 <= 64 &&
+                  kTileCtrWord + 8 <= kCountWords, "counter block");
 
 // PU shape of each class (W, H).  Order: by area, then width.
 constexpr int kClassW[kNumClasses] = {4, 8, 8, 4, 16, 8, 16, 12, 16, 16, 8, 32,
@@ -190,23 +200,28 @@ struct Schedule;
 // Work buffers (device) for one batch.
 struct WorkBufs {
   uint8_t* cls;          // [n] class id, 255 = invalid
-  int32_t* perm;         // [n] jobs grouped by class (original index)
+  int32_t* perm;         // jobs grouped by class (original index): a refinement batch's class c at
+                         // [c * perm_cap, + its count) (k_front); the integer search's classes densely in [0, n)
   int32_t* koff;         // [n] BatchArgs::koff as k_classify writes it (packed batches)
   int32_t* counts;       // [kNumClasses + 1]: per-class count, [24] = invalid jobs
-  int32_t* counts_next;  // the other counter block: k_scatter zeroes it for the next batch
+  int32_t* counts_next;  // the other counter block: k_front's last workgroup zeroes it for the next batch
   int32_t* cursor;       // [kNumClasses]
   int32_t* blk_agg;      // [nblk * 9] per-block max of the NN writer indices
   int32_t* blk_prefix;   // [nblk * 9] exclusive prefix (carry-in) per block
   uint32_t* nn_state;    // 2 x 12 words: slot[8], c, pu_h, pu_w, written
-  Schedule* sched;       // built on the device by k_scatter (block 0) from counts
+  Schedule* sched;       // built on the device by k_front's last workgroup from the class totals
   int32_t* tile_ctr;     // [8] lane-kernel tile queue heads (part of the counter block)
   fme_mv_result* mv_out; // compact per-job output (fme_refine_mv*), or null
+  int32_t perm_cap;      // jobs per class region of perm (the context's job capacity, >= n); the last
+                         // member, so that the search kernels find the others where they were
 };
 // The search record of job i (the search writes its records in call order; the tail completes them).
 __device__ __forceinline__ const fme_result* search_rec(const BatchArgs& a, const WorkBufs&, int i) { return a.res + i; }
 
-// Schedule of the search kernel (k_scatter builds it on the device): class c's jobs are
+// Schedule of the search kernel (k_front builds it on the device): class c's jobs are
 // perm[class_off[c] .. + class_cnt[c]) and its 64-lane wave tiles [prefix[c], prefix[c+1]).
+// class_off[c] = c * WorkBufs::perm_cap: the class regions do not depend on the counts, so a
+// workgroup writes perm before the totals are known, and they are not adjacent.
 struct Schedule {
   int32_t prefix[kNumClasses + 1];
   int32_t class_off[kNumClasses];
@@ -216,11 +231,23 @@ struct Schedule {
   // and its queue lists the band class by class in the order lane_class_at: xq[x][i] = the queue's
   // tiles before class lane_class_at(i); xq[x][kNumClasses] = its length.
   int32_t xq[8][kNumClasses + 1];
-  int32_t invalid;            // jobs rejected by k_classify (the whole batch is then skipped)
+  int32_t invalid;            // jobs rejected by k_front (the whole batch is then skipped)
   int32_t pad_[3];
 };
+// The jobs of classes [c0, c1) in class order: how many there are, and where the q-th of them sits
+// in perm (the kernels that walk several classes as one list: fme_px.hip).
+__device__ __forceinline__ int sched_count(const Schedule* sc, int c0, int c1) {
+  int n = 0;
+  for (int c = c0; c < c1; c++) n += sc->class_cnt[c];
+  return n;
+}
+__device__ __forceinline__ int sched_perm_index(const Schedule* sc, int c0, int c1, int q) {
+  int c = c0;
+  for (; c < c1 - 1 && q >= sc->class_cnt[c]; c++) q -= sc->class_cnt[c];
+  return sc->class_off[c] + q;
+}
 
-// What k_scatter's schedule needs to know about the search kernel: lanes per PU of each class (its unit
+// What the schedule needs to know about the search kernel: lanes per PU of each class (its unit
 // count rounded up to a power of two).
 struct SchedParams {
   int32_t lanes[kNumClasses];
@@ -284,9 +311,15 @@ struct TzChain {
 hipError_t launch_tz_levels(const TzArgs& ta, const TzChain& ch, const int32_t* h_lvl_off, int bit_depth, hipStream_t s);
 
 // Host-side launch helpers (fme_kernels.hip).
+// A refinement batch's front end in one pass: validation, class, perm (class c at c * w.perm_cap),
+// the NN writer maxima; the workgroup that finishes last writes *w.sched (block ranges, XCD queues,
+// invalid count) and w.blk_prefix and zeroes w.counts_next
+hipError_t launch_front(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, hipStream_t s);
+// The integer search's two passes (its class offsets are dense and its schedule is built on the host):
+// validation, class and the class histogram in w.counts,
 hipError_t launch_classify(const BatchArgs& a, const WorkBufs& w, hipStream_t s);
-// every block: w.counts -> class offsets (LDS), jobs grouped by class; block 0 also writes *w.sched
-// (class offsets, block ranges, XCD queues, invalid count) and zeroes w.counts_next
+// then w.counts -> class offsets and the jobs grouped by class in perm[0, n) (block 0 also writes
+// *w.sched with those offsets, which the integer search does not read, and zeroes w.counts_next)
 hipError_t launch_scatter(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, hipStream_t s);
 // 12 words of NN state written to dst in stream order (reset / set_state)
 hipError_t launch_put_state(uint32_t* dst, const uint32_t* v12, hipStream_t s);

@@ -1,17 +1,18 @@
 // fme_kernels.hip — CDNA4 (gfx950) kernels of the fractional-pel motion-estimation path.
 //
-// One batch of PU jobs runs as five launches (tables, classify, scatter, search, nn_tail).  The
+// One batch of PU jobs runs as four launches (tables, front, search, nn_tail).  The
 // jobs are read where the caller put them, through load_job (fme_device.h): fme_job rows, or the
 // 16-byte fme_job_packed rows of the packed entry points expanded in registers; no kernel writes
 // an unpacked copy.
-//   classify   per job: validation, PU-shape class, EMI push count, and for packed rows the keyed
-//              jobs' key offsets (a scan per 64-job group from key_base); per block: class
-//              histogram and the max of the NN "last writer" indices (first pass of a prefix-max
-//              scan).
-//   scatter    the schedule from the histogram (class offsets in every block; block 0 publishes
-//              the search's tile ranges and per-XCD queues), jobs grouped by class
-//              (block-aggregated atomics), and the other counter block zeroed for the next batch,
+//   front      per job: validation, PU-shape class, and for packed rows the keyed jobs' key
+//              offsets (a scan per 64-job group from key_base); per block: the jobs grouped by
+//              class straight into perm (class regions a fixed distance apart) and the max of the
+//              NN "last writer" indices; the block that finishes last: the schedule from the class
+//              totals (the search's tile ranges and per-XCD queues), the prefix-max of the writer
+//              indices over the blocks, and the other counter block zeroed for the next batch,
 //              which therefore needs no fill dispatch.
+//              (The integer search keeps the two passes this replaced, k_classify and k_scatter:
+//              its class offsets are dense and its schedule is built on the host.)
 //   search     EMI square step + FracDIF per tile of same-shape PUs (fme_lane.hip, fme_lane10.hip).
 //   nn_tail    prefix-max over jobs resolves which earlier job last wrote each array_e slot
 //              (the reference's stale global state, TEncSearch.cpp:55-57, 198-201), then
@@ -77,31 +78,32 @@ struct ClassLut {
 };
 __constant__ ClassLut kClassLut = ClassLut();
 
-// All of a block's loads (its 4 jobs per lane, the class table, the picture descriptors) are
-// issued before any of them is used: the kernel is a few dependent memory latencies long.
-__global__ __launch_bounds__(kBlock) void k_classify(BatchArgs a, WorkBufs w) {
-  constexpr int Q = kJobsPerScanBlock / kBlock;
-  __shared__ int32_t hist[kNumClasses + 1];
-  __shared__ int32_t agg[9];
-  __shared__ uint8_t lut[256];
-  __shared__ int32_t pic_w[FME_MAX_PICTURES], pic_h[FME_MAX_PICTURES];  // pic_w -1: slot unset
+// What a workgroup holds in LDS to validate its jobs.
+struct FrontTables {
+  uint8_t lut[256];
+  int32_t pic_w[FME_MAX_PICTURES], pic_h[FME_MAX_PICTURES];  // pic_w -1: slot unset
+  int32_t keys_bad;
+};
+constexpr int kFrontQ = kJobsPerScanBlock / kBlock;   // jobs per lane: base + q * kBlock + tid
+
+// A workgroup's jobs, every load issued before any is used (the front end is a few dependent memory
+// latencies long).
+__device__ __forceinline__ void front_load(const BatchArgs& a, const WorkBufs& w, int base, fme_job (&jb)[kFrontQ]) {
   const int tid = threadIdx.x;
-  const int base = blockIdx.x * kJobsPerScanBlock;
-  fme_job jb[Q];
   if (a.pjobs) {
     // Packed rows: a wave's 64 lanes hold one 64-job group (base and q * kBlock are multiples of
     // 64), whose keyed blocks follow key_base[group] densely in job order, so a job's key offset
     // is the base plus the exclusive sum of w*h over the group's earlier keyed jobs.  Groups
     // without a keyed job (every group of a uni-pred batch) scan and write nothing.
-    job_u4 row[Q];
+    job_u4 row[kFrontQ];
 #pragma unroll
-    for (int q = 0; q < Q; q++) {
+    for (int q = 0; q < kFrontQ; q++) {
       const int i = base + q * kBlock + tid;
       row[q] = job_u4{0u, 0u, 0u, 0u};
       if (i < a.n) row[q] = packed_row(a, i);
     }
 #pragma unroll
-    for (int q = 0; q < Q; q++) {
+    for (int q = 0; q < kFrontQ; q++) {
       const int i = base + q * kBlock + tid;
       const bool keyed_q = i < a.n && packed_keyed(row[q].y);
       int ko = -1;
@@ -123,22 +125,66 @@ __global__ __launch_bounds__(kBlock) void k_classify(BatchArgs a, WorkBufs w) {
     }
   } else {
 #pragma unroll
-    for (int q = 0; q < Q; q++) {
+    for (int q = 0; q < kFrontQ; q++) {
       const int i = base + q * kBlock + tid;
       if (i < a.n) jb[q] = load_job(a, i);
     }
   }
-  __shared__ int32_t keys_bad, keyed;
-  if (tid == 0) {
-    keys_bad = a.key_invalid ? *a.key_invalid : 0;
-    keyed = 0;
-  }
-  lut[tid] = kClassLut.v[tid];
+}
+
+// The class table, the picture sizes and the key flag, one entry per lane (before the workgroup's barrier).
+__device__ __forceinline__ void front_tables(const BatchArgs& a, FrontTables& T) {
+  const int tid = threadIdx.x;
+  if (tid == 0) T.keys_bad = a.key_invalid ? *a.key_invalid : 0;
+  T.lut[tid] = kClassLut.v[tid];
   if (tid < FME_MAX_PICTURES) {
     const PicDesc p = a.pics[tid];
-    pic_w[tid] = p.luma ? p.width : -1;
-    pic_h[tid] = p.height;
+    T.pic_w[tid] = p.luma ? p.width : -1;
+    T.pic_h[tid] = p.height;
   }
+}
+
+// Job i's class; 255 for a shape that is no HEVC inter PU and for what would make the search read
+// undefined memory.
+__device__ __forceinline__ int front_class(const BatchArgs& a, const FrontTables& T, const fme_job& j, int i) {
+  const int c = ((j.w | j.h) & 3) == 0 && j.w >= 4 && j.w <= 64 && j.h >= 4 && j.h <= 64
+                    ? T.lut[((j.w >> 2) - 1) * 16 + (j.h >> 2) - 1] : 255;
+  bool ok = j.ref_id < FME_MAX_PICTURES && j.lambda_id < FME_MAX_LAMBDAS && T.pic_w[j.ref_id] >= 0;
+  if (ok) {
+    if (j.key_offset >= 0) {
+      ok = (int64_t)j.key_offset + (int64_t)j.w * j.h <= a.n_keys && T.keys_bad == 0;
+    } else {
+      ok = j.org_id < FME_MAX_PICTURES && T.pic_w[j.org_id] >= 0 &&
+           (int)j.x + j.w <= T.pic_w[j.org_id] && (int)j.y + j.h <= T.pic_h[j.org_id];
+    }
+  }
+  // FME_JOB_NN_IN: its input row must be bound (fme_set_nn_inputs)
+  if ((j.flags & FME_JOB_NN_IN) && (!a.nn_in || i >= a.nn_in_cap)) ok = false;
+  return ok ? c : 255;
+}
+
+// The NN "last writer" indices job i raises (first pass of the tail's prefix-max scan).
+__device__ __forceinline__ void front_writers(const fme_job& j, int i, int (&mx)[9]) {
+  if (!nn_writes_c(j)) return;
+  const int np = nn_pushes(j);
+#pragma unroll
+  for (int s = 0; s < 8; s++)
+    if (np > s) mx[s] = max(mx[s], i);
+  mx[8] = max(mx[8], i);
+}
+
+// The integer search's first pass: class per job, the class histogram in w.counts.
+__global__ __launch_bounds__(kBlock) void k_classify(BatchArgs a, WorkBufs w) {
+  __shared__ FrontTables T;
+  __shared__ int32_t hist[kNumClasses + 1];
+  __shared__ int32_t agg[9];
+  __shared__ int32_t keyed;
+  const int tid = threadIdx.x;
+  const int base = blockIdx.x * kJobsPerScanBlock;
+  fme_job jb[kFrontQ];
+  front_load(a, w, base, jb);
+  front_tables(a, T);
+  if (tid == 0) keyed = 0;
   if (tid < kNumClasses + 1) hist[tid] = 0;
   if (tid < 9) agg[tid] = -1;
   __syncthreads();
@@ -146,35 +192,15 @@ __global__ __launch_bounds__(kBlock) void k_classify(BatchArgs a, WorkBufs w) {
 #pragma unroll
   for (int f = 0; f < 9; f++) mx[f] = -1;
 #pragma unroll
-  for (int q = 0; q < Q; q++) {
+  for (int q = 0; q < kFrontQ; q++) {
     const int i = base + q * kBlock + tid;
     if (i < a.n) {
       const fme_job& j = jb[q];
-      int c = ((j.w | j.h) & 3) == 0 && j.w >= 4 && j.w <= 64 && j.h >= 4 && j.h <= 64
-                  ? lut[((j.w >> 2) - 1) * 16 + (j.h >> 2) - 1] : 255;
-      // reject what would make the search read undefined memory
-      bool ok = j.ref_id < FME_MAX_PICTURES && j.lambda_id < FME_MAX_LAMBDAS && pic_w[j.ref_id] >= 0;
-      if (ok) {
-        if (j.key_offset >= 0) {
-          ok = (int64_t)j.key_offset + (int64_t)j.w * j.h <= a.n_keys && keys_bad == 0;
-        } else {
-          ok = j.org_id < FME_MAX_PICTURES && pic_w[j.org_id] >= 0 &&
-               (int)j.x + j.w <= pic_w[j.org_id] && (int)j.y + j.h <= pic_h[j.org_id];
-        }
-      }
-      // FME_JOB_NN_IN: its input row must be bound (fme_set_nn_inputs)
-      if ((j.flags & FME_JOB_NN_IN) && (!a.nn_in || i >= a.nn_in_cap)) ok = false;
-      if (!ok) c = 255;
+      const int c = front_class(a, T, j, i);
       w.cls[i] = (uint8_t)c;
       atomicAdd(&hist[c == 255 ? kNumClasses : c], 1);
       if (j.key_offset >= 0) atomicAdd(&keyed, 1);
-      if (nn_writes_c(j)) {
-        const int np = nn_pushes(j);
-#pragma unroll
-        for (int s = 0; s < 8; s++)
-          if (np > s) mx[s] = max(mx[s], i);
-        mx[8] = max(mx[8], i);
-      }
+      front_writers(j, i, mx);
     }
   }
 #pragma unroll
@@ -187,11 +213,8 @@ __global__ __launch_bounds__(kBlock) void k_classify(BatchArgs a, WorkBufs w) {
 }
 
 // ---------------------------------------------------------------------------------------
-// scatter, with the schedule: the class histogram -> class offsets, the search kernel's block
-// ranges and the lane kernels' per-XCD tile queues, all on the device, so a batch needs no host
-// round trip between classify and search.  Every block scans the 24 counts for the class offsets
-// it scatters to (one wave, one lane per class); block 0 goes on to write the whole Schedule,
-// which only kernels after the scatter read, and zeroes the other counter block for the next batch.
+// The schedule: class totals -> the search kernel's block ranges and the lane kernels' per-XCD tile
+// queues, all on the device, so a batch needs no host round trip between the front end and the search.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ int wave_excl_scan(int v) {
   const int lane = (int)threadIdx.x & 63;
@@ -204,14 +227,12 @@ __device__ __forceinline__ int wave_excl_scan(int v) {
   return s - v;
 }
 
-// Lane c < kNumClasses of one wave: class c's count; returns its offset in class order.
-// publish: also write *sc (block ranges, XCD queues, the invalid count).
-__device__ __forceinline__ int build_schedule(const int32_t* __restrict__ counts, const SchedParams& p, Schedule* sc,
-                                              bool publish) {
+// One wave; lane c < kNumClasses holds class c's count (0 in every lane of a rejected batch, inv > 0).
+// Returns class c's offset in perm: c * cap, or with cap = 0 the dense one (the counts' exclusive sum).
+// publish: also write *sc (class offsets and counts, block ranges, XCD queues, the invalid count).
+__device__ __forceinline__ int build_schedule(int cnt, int inv, const SchedParams& p, Schedule* sc, bool publish, int cap) {
   const int c = (int)threadIdx.x & 63;
-  const int inv = counts[kNumClasses];
-  const int cnt = (c < kNumClasses && inv == 0) ? counts[c] : 0;
-  const int off = wave_excl_scan(cnt);
+  const int off = cap > 0 ? c * cap : wave_excl_scan(cnt);
   if (!publish) return off;   // wave-uniform
   const int nb = cnt > 0 ? (int)(((long long)cnt * p.lanes[c < kNumClasses ? c : 0] + 63) / 64) : 0;   // 64-lane wave tiles
   if (c < kNumClasses) {
@@ -235,6 +256,208 @@ __device__ __forceinline__ int build_schedule(const int32_t* __restrict__ counts
   return off;
 }
 
+// ---------------------------------------------------------------------------------------
+// The front end of a refinement batch in one pass.  Every workgroup, for its 1,024 jobs: class and
+// validation per job (cls), the jobs' ranks per class in call order (a ballot per class a wave
+// holds, then a scan over the workgroup's 16 64-job segments: no atomic per job), its base in each
+// class from one returning atomicAdd on the class cursor, and perm[c * perm_cap + base + rank] = i at
+// once: the class regions of perm are perm_cap jobs apart, so no workgroup needs the totals.  The
+// NN writer maxima go to blk_agg with write-through stores.  Once those and the atomics have been
+// performed the workgroup draws a ticket; the workgroup that draws the last one (nobody waits or
+// polls, so a workgroup that has not started holds nothing up) is the only one that reads other
+// workgroups' data, after an agent-scope acquire and with agent-scope loads, as they ran on other
+// XCDs: the class totals (the cursors' final values) become the Schedule, blk_agg's exclusive
+// prefix-max over the scan blocks becomes blk_prefix (k_nn_tail's carry-in of the stale-state
+// scan), and the other counter block is zeroed for the next batch, which therefore needs no fill
+// dispatch.  What the kernel's 37 us are made of, step by step: DESIGN.md §5 "One-pass front end".
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ int ld_agent(const int32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_agent(int32_t* p, int v) {   // a write-through store: past this XCD's L2
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// blk_prefix[b] = max of blk_agg[0 .. b) per field, for nb scan blocks, by one whole workgroup: each
+// lane takes a contiguous run of blocks, the lanes' run maxima are scanned, each lane walks its run again.
+// The loads go out four blocks (36 words) at a time before any is used: this is the one workgroup
+// the whole kernel waits for.  A lane's run of up to four blocks (1,024 scan blocks, a 1080p frame
+// has 843) stays in registers for the second walk.
+constexpr int kPfxAhead = 4;
+__device__ __forceinline__ void front_agg_load(const WorkBufs& w, int b, int b1, int (&v)[kPfxAhead][9]) {
+#pragma unroll
+  for (int k = 0; k < kPfxAhead; k++) {
+#pragma unroll
+    for (int f = 0; f < 9; f++) v[k][f] = b + k < b1 ? ld_agent(w.blk_agg + (b + k) * 9 + f) : -1;
+  }
+}
+__device__ __forceinline__ void front_blk_prefix(const WorkBufs& w, int nb) {
+  __shared__ int32_t red[kBlock / 64][9];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int per = (nb + kBlock - 1) / kBlock;
+  const int b0 = min(tid * per, nb), b1 = min(b0 + per, nb);
+  int m[9], v[kPfxAhead][9];
+#pragma unroll
+  for (int f = 0; f < 9; f++) m[f] = -1;
+  for (int b = b0; b < b1 || b == b0; b += kPfxAhead) {   // (once at least: v is the lane's run when per <= kPfxAhead)
+    front_agg_load(w, b, b1, v);
+#pragma unroll
+    for (int k = 0; k < kPfxAhead; k++) {
+#pragma unroll
+      for (int f = 0; f < 9; f++) m[f] = max(m[f], v[k][f]);
+    }
+  }
+  int run[9];   // the maxima of the lanes before this one: inclusive scan, then shifted by one lane
+#pragma unroll
+  for (int f = 0; f < 9; f++) {
+    int s = m[f];
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(s, off, 64);
+      if (lane >= off) s = max(s, o);
+    }
+    if (lane == 63) red[wv][f] = s;
+    const int e = __shfl_up(s, 1, 64);
+    run[f] = lane ? e : -1;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int f = 0; f < 9; f++)
+    for (int q = 0; q < wv; q++) run[f] = max(run[f], red[q][f]);
+  for (int b = b0; b < b1; b += kPfxAhead) {
+    if (per > kPfxAhead) front_agg_load(w, b, b1, v);
+#pragma unroll
+    for (int k = 0; k < kPfxAhead; k++) {
+      if (b + k < b1) {
+#pragma unroll
+        for (int f = 0; f < 9; f++) {
+          w.blk_prefix[(b + k) * 9 + f] = run[f];
+          run[f] = max(run[f], v[k][f]);
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_front(BatchArgs a, WorkBufs w, SchedParams sp) {
+  constexpr int kSeg = kFrontQ * (kBlock / 64);   // 64-job segments of the workgroup, in call order
+  __shared__ FrontTables T;
+  __shared__ int32_t seg[kSeg][kNumClasses + 1];  // jobs per class ([kNumClasses]: invalid), then their exclusive sums
+  __shared__ int32_t basep[kNumClasses];
+  __shared__ int32_t agg[9];
+  __shared__ int32_t keyed, last;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int base = blockIdx.x * kJobsPerScanBlock;
+  fme_job jb[kFrontQ];
+  front_load(a, w, base, jb);
+  front_tables(a, T);
+  if (tid == 0) keyed = 0;
+  for (int k = tid; k < kSeg * (kNumClasses + 1); k += kBlock) (&seg[0][0])[k] = 0;
+  if (tid < 9) agg[tid] = -1;
+  __syncthreads();
+  int mx[9], cls[kFrontQ], rank[kFrontQ];
+#pragma unroll
+  for (int f = 0; f < 9; f++) mx[f] = -1;
+  int nkeyed = 0;
+#pragma unroll
+  for (int q = 0; q < kFrontQ; q++) {
+    const int i = base + q * kBlock + tid;
+    const bool valid = i < a.n;
+    cls[q] = kNumClasses;
+    rank[q] = 0;
+    if (valid) {
+      const fme_job& j = jb[q];
+      const int c = front_class(a, T, j, i);
+      w.cls[i] = (uint8_t)c;
+      cls[q] = c == 255 ? kNumClasses : c;
+      front_writers(j, i, mx);
+    }
+    nkeyed += __popcll(__ballot(valid && jb[q].key_offset >= 0));
+    // ranks inside the wave's segment: one ballot per class the segment holds
+    int32_t* sg = seg[q * (kBlock / 64) + (tid >> 6)];
+    unsigned long long rem = __ballot(valid);
+    while (rem) {   // wave-uniform
+      const int cl = __shfl(cls[q], __ffsll((long long)rem) - 1);
+      const unsigned long long m = __ballot(valid && cls[q] == cl);
+      if (valid && cls[q] == cl) {
+        rank[q] = __popcll(m & ((1ull << lane) - 1ull));
+        if (rank[q] == 0) sg[cl] = __popcll(m);
+      }
+      rem &= ~m;
+    }
+  }
+  if (lane == 0 && nkeyed) atomicAdd(&keyed, nkeyed);
+  // the wave's maxima first: 64 lanes' atomics on one LDS word are served one after the other
+#pragma unroll
+  for (int f = 0; f < 9; f++) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx[f] = max(mx[f], __shfl_xor(mx[f], off));
+  }
+  if (lane < 9) {
+    int v = mx[0];
+#pragma unroll
+    for (int f = 1; f < 9; f++) v = lane == f ? mx[f] : v;
+    if (v >= 0) atomicMax(&agg[lane], v);
+  }
+  __syncthreads();
+  if (tid < kNumClasses + 2) {
+    // one atomic instruction per workgroup, all in one 128-byte line (fme_device.h, counter block):
+    // lanes 0..23 the class cursors, whose old values are the workgroup's bases; lanes 24, 25 the
+    // invalid and keyed counts
+    int tot = keyed;
+    if (tid < kNumClasses + 1) {
+      tot = 0;
+      for (int s = 0; s < kSeg; s++) {
+        const int t = seg[s][tid];
+        seg[s][tid] = tot;
+        tot += t;
+      }
+    }
+    const int old = tot ? atomicAdd(&w.cursor[tid], tot) : 0;
+    if (tid < kNumClasses) basep[tid] = old;
+  } else if (tid >= 64 && tid < 64 + 9) {
+    st_agent(w.blk_agg + blockIdx.x * 9 + tid - 64, agg[tid - 64]);
+  }
+  // What the last workgroup reads of this one went out as agent-scope atomics and write-through
+  // stores; every wave waits until its own have been performed, then lane 0 draws the ticket.  (An
+  // agent-scope release fence here instead writes the XCD's L2 back once per workgroup, with the
+  // other workgroups' perm and cls stores in it: 8 us more per batch)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0)
+    last = __hip_atomic_fetch_add(&w.counts[kTicketWord], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+#pragma unroll
+  for (int q = 0; q < kFrontQ; q++) {
+    const int i = base + q * kBlock + tid;
+    const int c = cls[q];
+    if (c < kNumClasses)   // (jobs past a.n hold kNumClasses)
+      w.perm[(size_t)c * w.perm_cap + basep[c] + seg[q * (kBlock / 64) + (tid >> 6)][c] + rank[q]] = i;
+  }
+  __syncthreads();
+  if (!last) return;
+  // ---- the last workgroup: every other one has released its counts and blk_agg ----
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+  int inv = 0, tot = 0;   // wave 0: the totals, asked for before the prefix pass and used after it
+  if (tid < 64) {
+    inv = ld_agent(w.cursor + kNumClasses);
+    tot = tid < kNumClasses ? ld_agent(w.cursor + tid) : 0;
+  } else if (tid < 64 + kCountWords) {
+    w.counts_next[tid - 64] = 0;   // the next batch's counter block (also when this one is rejected)
+  }
+  front_blk_prefix(w, (int)gridDim.x);
+  if (tid < 64) build_schedule(inv == 0 ? tot : 0, inv, sp, w.sched, true, w.perm_cap);
+}
+
+// ---------------------------------------------------------------------------------------
+// The integer search's second pass: the class histogram -> dense class offsets (every block, one
+// wave, one lane per class) and the jobs grouped by class (block-aggregated atomics).  Block 0 also
+// writes the Schedule and zeroes the other counter block, as it did when refinement batches ran
+// through this kernel; the integer search reads neither.
+// ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_scatter(BatchArgs a, WorkBufs w, SchedParams sp) {
   __shared__ int32_t cnt[kNumClasses], basep[kNumClasses], class_off[kNumClasses];
   const int tid = threadIdx.x;
@@ -248,10 +471,11 @@ __global__ __launch_bounds__(kBlock) void k_scatter(BatchArgs a, WorkBufs w, Sch
     if (i < a.n) cls[q] = w.cls[i];
   }
   if (tid < 64) {
-    const int off = build_schedule(w.counts, sp, w.sched, blockIdx.x == 0);
+    const int inv = w.counts[kNumClasses];
+    const int off = build_schedule((tid < kNumClasses && inv == 0) ? w.counts[tid] : 0, inv, sp, w.sched, blockIdx.x == 0, 0);
     if (tid < kNumClasses) class_off[tid] = off;
   } else if (blockIdx.x == 0 && tid < 64 + kCountWords) {
-    w.counts_next[tid - 64] = 0;   // the next batch's counter block (also when this one is rejected)
+    w.counts_next[tid - 64] = 0;
   }
   if (w.counts[kNumClasses]) return;   // rejected batch: nothing downstream reads the grouping
   if (tid < kNumClasses) cnt[tid] = 0;
@@ -266,33 +490,6 @@ __global__ __launch_bounds__(kBlock) void k_scatter(BatchArgs a, WorkBufs w, Sch
   for (int q = 0; q < kJobsPerScanBlock / kBlock; q++) {
     const int i = base + q * kBlock + tid;
     if (cls[q] < kNumClasses) w.perm[class_off[cls[q]] + basep[cls[q]] + rank[q]] = i;
-  }
-  // Exclusive prefix-max of the NN-writer aggregates over the blocks before this one: k_nn_tail's
-  // carry-in of the stale-state scan.  It depends on k_classify only, so it is computed here,
-  // before the search, instead of by a serial pass between the search and the tail.
-  __shared__ int32_t red[kBlock / 64][9];
-  int m[9];
-#pragma unroll
-  for (int f = 0; f < 9; f++) m[f] = -1;
-  for (int b = tid; b < (int)blockIdx.x; b += kBlock) {
-#pragma unroll
-    for (int f = 0; f < 9; f++) m[f] = max(m[f], w.blk_agg[b * 9 + f]);
-  }
-#pragma unroll
-  for (int f = 0; f < 9; f++) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m[f] = max(m[f], __shfl_xor(m[f], off));
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int f = 0; f < 9; f++) red[tid >> 6][f] = m[f];
-  }
-  __syncthreads();
-  if (tid < 9) {
-    int r = red[0][tid];
-#pragma unroll
-    for (int q = 1; q < kBlock / 64; q++) r = max(r, red[q][tid]);
-    w.blk_prefix[blockIdx.x * 9 + tid] = r;
   }
 }
 
@@ -533,6 +730,11 @@ void k_nn_tail(BatchArgs a, WorkBufs w, const float* __restrict__ nnp_g, int sta
 // host launch helpers
 // ---------------------------------------------------------------------------------------
 static int nblocks(int n) { return (n + kJobsPerScanBlock - 1) / kJobsPerScanBlock; }
+
+hipError_t launch_front(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, hipStream_t s) {
+  hipLaunchKernelGGL(k_front, dim3(nblocks(a.n)), dim3(kBlock), 0, s, a, w, p);
+  return hipGetLastError();
+}
 
 hipError_t launch_classify(const BatchArgs& a, const WorkBufs& w, hipStream_t s) {
   hipLaunchKernelGGL(k_classify, dim3(nblocks(a.n)), dim3(kBlock), 0, s, a, w);

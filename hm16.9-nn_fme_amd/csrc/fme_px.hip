@@ -253,9 +253,10 @@ __global__ __launch_bounds__(kPxNT) void k_search_px(BatchArgs a, WorkBufs wb) {
   if (wb.sched->invalid) return;   // rejected batch: the tail marks every record
   constexpr int HR = 14 - BD < 2 ? 2 : 14 - BD, SH1 = 6 - HR, DSH = BD - 8;
   const int tid = (int)threadIdx.x, lane = tid & 63;
-  // the PUs wider or taller than 16 (class order from k_scatter; k_search_px_wave takes the rest)
-  for (int q = wb.sched->class_off[kPxSmallClasses] + (int)blockIdx.x; q < a.n; q += gridDim.x) {
-    const int i = wb.perm[q];
+  // the PUs wider or taller than 16 (class order from k_front; k_search_px_wave takes the rest)
+  const int n_big = sched_count(wb.sched, kPxSmallClasses, kNumClasses);
+  for (int q = (int)blockIdx.x; q < n_big; q += gridDim.x) {
+    const int i = wb.perm[sched_perm_index(wb.sched, kPxSmallClasses, kNumClasses, q)];
     const fme_job j = load_job(a, i);
     const int w = j.w, h = j.h, ws = w + 10, wh = h + 10;
     // ---- 1. window and key -------------------------------------------------------------------
@@ -506,9 +507,9 @@ __global__ __launch_bounds__(kPxNT) __attribute__((amdgpu_waves_per_eu(FME_PXW_W
   constexpr int HR = 14 - BD < 2 ? 2 : 14 - BD, SH1 = 6 - HR, DSH = BD - 8;
   const int lane = (int)threadIdx.x & 63, wid = (int)threadIdx.x >> 6;
   PxSmall& L = Ls[wid];
-  const int n_small = wb.sched->class_off[kPxSmallClasses];
+  const int n_small = sched_count(wb.sched, 0, kPxSmallClasses);
   for (int q = (int)blockIdx.x * kPxWaves + wid; q < n_small; q += (int)gridDim.x * kPxWaves) {
-    const int i = __builtin_amdgcn_readfirstlane(wb.perm[q]);
+    const int i = __builtin_amdgcn_readfirstlane(wb.perm[sched_perm_index(wb.sched, 0, kPxSmallClasses, q)]);
     const fme_job j = load_job(a, i);
     const int w = j.w, h = j.h, ws = w + 10, wh = h + 10;
     // ---- 1. window and key (rows of the window per pass: 64 / ws) ----

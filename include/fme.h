@@ -742,7 +742,8 @@ int fme_mc_last_ms(fme_ctx* ctx, float* ms);
 /* ---- instrumentation (an extension; the reference has no counterpart) ------------------- *
  * With profiling on, fme_refine/fme_refine_device record HIP events around each kernel of
  * the batch on the streams the kernels run on.  Device milliseconds, FME_NUM_TIMINGS values:
- * [0] classify, [1] schedule + scatter, [2] search phase (EMI + FracDIF), [3] NN + tail,
+ * [0] the front end (one kernel classifies, scatters and builds the schedule), [1] 0 (the scatter's
+ * own launch in earlier versions), [2] search phase (EMI + FracDIF), [3] NN + tail,
  * [4] whole batch (first kernel start to last kernel end), [5] the search kernel, [6] 0 (an
  * auxiliary search kernel in earlier versions; every PU shape now runs in the one kernel).
  * fme_last_timings waits for the last profiled batch.  fme_accumulated_timings returns the

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Timeline of a rocprofv3 --kernel-trace --memory-copy-trace run of bench.py: the last steps'
 kernels and copies in start order with their offsets and durations, and per-step spacing
-(k_classify to k_classify).
+(k_front to k_front; k_classify in traces of older trees).
 
 usage: timeline.py TRACE_DIR [steps_to_show] [first_step]
-first_step: index of the first k_classify launch shown (default: the last steps_to_show steps;
+first_step: index of the first k_front launch shown (default: the last steps_to_show steps;
 bench.py runs the PCIe-inclusive pass before the resident one, so its steps come first)."""
 import csv
 import glob
@@ -27,12 +27,12 @@ def main():
             size = r.get("Size", r.get("Bytes", ""))
             ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "C", f"{kind} {size}", ""))
     ev.sort()
-    cls = [e for e in ev if e[2] == "K" and "k_classify" in e[3]]
+    cls = [e for e in ev if e[2] == "K" and ("k_front" in e[3] or "k_classify" in e[3])]
     if len(cls) < show + 1:
         print("too few steps", len(cls))
         return
     gaps = [(cls[i + 1][0] - cls[i][0]) / 1e3 for i in range(len(cls) - 1)]
-    print("classify-to-classify (us):", [round(g) for g in gaps])
+    print("front-to-front (us):", [round(g) for g in gaps])
     i0 = len(cls) - show - 1 if first is None else first
     t0 = cls[i0][0]
     t1 = cls[min(i0 + show, len(cls) - 1)][0]
