@@ -23,12 +23,15 @@ namespace {
 thread_local std::string g_last_error = "";
 }  // namespace
 
-// counts buffer: two counter blocks of kCountWords (fme_device.h: three 128-byte lines with the
+// counts buffer: kOvBlocks counter blocks of kCountWords (fme_device.h: three 128-byte lines with the
 // integer search's class histogram and k_front's done ticket, the 24 scatter cursors with k_front's
-// invalid and keyed counts, and the 8 lane tile-queue heads), both zeroed at allocation.  A refinement batch counts in block counts_cur and its k_front (the workgroup that
-// finishes last) zeroes the other one, which the next batch uses: no fill dispatch per batch.  Whatever else touches the blocks (the integer
-// search, a batch whose launches failed midway) sets counts_dirty, and the next batch starts with
-// one hipMemsetAsync of both blocks (use_counts).
+// invalid and keyed counts, and the 8 lane tile-queue heads), all zeroed at allocation.  Batch k
+// counts in block k % kOvBlocks and its k_front (the workgroup that finishes last) zeroes the block
+// of batch k + 2: no fill dispatch per batch, and no block is zeroed while the batch before or
+// after, which may run beside this one on another stream, uses it (fme_overlap_host.h).  Whatever
+// else touches the blocks (the integer search, a batch whose launches failed midway) leaves them
+// in doubt (OverlapState::dirty), and the next batch starts, behind every batch in flight, with
+// one hipMemsetAsync of all blocks.
 
 int fme::fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -60,18 +63,19 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
   std::unique_ptr<fme_ctx> c(new fme_ctx());
   c->device = device;
   c->cfg = *cfg;
-  HIP_TRY(c->d_pics.reserve(FME_MAX_PICTURES));
-  HIP_TRY(c->d_mlambda.reserve(FME_MAX_LAMBDAS));
+  HIP_TRY(c->d_pics.reserve(kOvSlots * FME_MAX_PICTURES));
+  HIP_TRY(c->d_mlambda.reserve(kOvSlots * FME_MAX_LAMBDAS));
   HIP_TRY(c->d_nn.reserve(kNnPkFloats));
-  HIP_TRY(c->counts.reserve(2 * kCountWords));
-  HIP_TRY(hipMemset(c->counts.p, 0, 2 * kCountWords * sizeof(int32_t)));
-  HIP_TRY(c->d_sched.reserve(1));
+  HIP_TRY(c->counts.reserve(kOvBlocks * kCountWords));
+  HIP_TRY(hipMemset(c->counts.p, 0, kOvBlocks * kCountWords * sizeof(int32_t)));
+  HIP_TRY(c->d_sched.reserve(kOvSlots));
+  HIP_TRY(hipMemset(c->d_sched.p, 0, kOvSlots * sizeof(Schedule)));
+  for (auto& e : c->done_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   c->sched_p = sched_params();
   {
     const char* m10 = std::getenv("FME_MAIN10_SEARCH");
     c->main10_px = m10 && std::strcmp(m10, "px") == 0;
   }
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
   HIP_TRY(c->nn_state.reserve(24));
   HIP_TRY(hipMemset(c->nn_state.p, 0, 24 * sizeof(uint32_t)));
   HIP_TRY(c->d_key_invalid.reserve(1));
@@ -81,10 +85,12 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
     const size_t n = (size_t)cfg->max_jobs;
     const size_t nb = (n + kJobsPerScanBlock - 1) / kJobsPerScanBlock;
     if (n * kNumClasses > (size_t)INT32_MAX) return fail(FME_E_INVALID, "fme_create: max_jobs %d", cfg->max_jobs);
-    HIP_TRY(c->cls.reserve(n));
-    HIP_TRY(c->perm.reserve(n * kNumClasses));   // one region of n jobs per class (k_front)
-    HIP_TRY(c->blk_agg.reserve(nb * 9));
-    HIP_TRY(c->blk_prefix.reserve(nb * 9));
+    for (int b = 0; b < kOvSlots; b++) {
+      HIP_TRY(c->cls[b].reserve(n));
+      HIP_TRY(c->perm[b].reserve(n * kNumClasses));   // one region of n jobs per class (k_front)
+      HIP_TRY(c->blk_agg[b].reserve(nb * 9));
+      HIP_TRY(c->blk_prefix[b].reserve(nb * 9));
+    }
   }
   *out_ctx = c.release();
   return FME_OK;
@@ -92,6 +98,19 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
 
 }  // extern "C"
 static int srv_stop(fme_ctx* c);
+// The end event of the batch `back` batches ago (1: the last one), or null.
+static hipEvent_t done_event(const fme_ctx* c, int back) {
+  if (back < 1 || back > 2 || !c->ov.live[back - 1]) return nullptr;
+  return c->done_ev[(c->ov.seq - back) % fme_ctx::kDoneRing];
+}
+// s waits for the refinement batches in flight on other streams (at most two: a batch's tail waits
+// for the batch before it).
+static int wait_batches(fme_ctx* c, hipStream_t s) {
+  for (int back = 1; back <= 2; back++)
+    if (hipEvent_t e = done_event(c, back))
+      if (c->ov.stream[back - 1] != s) HIP_TRY(hipStreamWaitEvent(s, e, 0));
+  return FME_OK;
+}
 // Remember a stream this context issued work on (reads of its buffers may be queued there).
 static void note_stream(fme_ctx* c, hipStream_t s) {
   for (int i = 0; i < c->n_used_streams; i++)
@@ -114,6 +133,7 @@ static int drain_ctx(fme_ctx* c) {
 // read: drain_ctx waits for the streams this context has used (for the whole device only when it
 // used more than it tracks), and only when the buffer really grows.
 int fme::grow_keys(fme_ctx* c, size_t n) {
+  c->keys_fresh = true;   // its writer follows: the next batch waits for the batches in flight (one key buffer)
   if (n <= c->d_keys.cap) return FME_OK;
   FME_TRY(drain_ctx(c));   // no queued launch of this context still reads the old key buffer
   HIP_TRY(c->d_keys.reserve(n));
@@ -151,10 +171,16 @@ int fme_destroy(fme_ctx* c) {
   for (auto& e : c->ev_surf)
     if (e) (void)hipEventDestroy(e);
   c->d_pics.release(); c->d_mlambda.release(); c->d_keys.release(); c->d_nn.release(); c->d_net.release();
-  c->d_jobs.release(); c->d_res.release(); c->d_mv.release(); c->koff.release(); c->cls.release(); c->perm.release();
-  c->counts.release(); c->blk_agg.release(); c->blk_prefix.release(); c->nn_state.release();
+  c->d_jobs.release(); c->d_res.release(); c->d_res1.release(); c->d_mv.release();
+  for (int b = 0; b < kOvSlots; b++) {
+    c->koff[b].release(); c->cls[b].release(); c->perm[b].release(); c->blk_agg[b].release(); c->blk_prefix[b].release();
+  }
+  c->counts.release(); c->nn_state.release();
   c->d_sched.release();
-  if (c->ev_done) (void)hipEventDestroy(c->ev_done);
+  for (auto& e : c->done_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->state_read_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->stage) (void)hipHostFree(c->stage);
   if (c->single_stream) (void)hipStreamDestroy(c->single_stream);
   if (c->box) (void)hipHostFree(c->box);
@@ -296,6 +322,7 @@ int fme_set_keys(fme_ctx* c, const int16_t* keys, size_t count, void* stream) {
   FME_TRY(srv_stop(c));
   FME_TRY(grow_keys(c, count));
   hipStream_t s = static_cast<hipStream_t>(stream);
+  FME_TRY(wait_batches(c, s));   // a batch in flight on another stream may still read the keys
   if (count) HIP_TRY(hipMemcpyAsync(c->d_keys.p, keys, count * sizeof(int16_t), hipMemcpyHostToDevice, s));
   // fresh host keys: a rejection left by an earlier device build no longer applies (fme.h: rejected
   // "until keys are built again"), in stream order with the upload
@@ -424,11 +451,22 @@ int fme_nn_copy_state_device(fme_ctx* c, uint32_t* d_out12, void* stream) {
   if (!c || !d_out12) return fail(FME_E_INVALID, "fme_nn_copy_state_device: null argument");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (c->state_pending)
+  if (c->state_pending) {
     HIP_TRY(launch_put_state(d_out12, c->pending_state, s));
-  else
-    HIP_TRY(hipMemcpyAsync(d_out12, c->nn_state.p + 12 * c->state_cur, 12 * sizeof(uint32_t),
-                           hipMemcpyDeviceToDevice, s));
+    return FME_OK;
+  }
+  // The copy reads the words the last batch's tail wrote: s waits for that batch where it ran on
+  // another stream.  The next batch may set or reset those words before its tail, on another
+  // stream again, so it waits for this read first (refine_batch): an event per copy, from a ring,
+  // recorded once per use; only the latest is ever waited for.
+  FME_TRY(wait_batches(c, s));
+  HIP_TRY(hipMemcpyAsync(d_out12, c->nn_state.p + 12 * c->state_cur, 12 * sizeof(uint32_t),
+                         hipMemcpyDeviceToDevice, s));
+  hipEvent_t& e = c->state_read_ev[c->state_reads++ % fme_ctx::kDoneRing];
+  if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(e, s));
+  c->state_read_last = e;
+  c->state_read_stream = s;
   return FME_OK;
 }
 
@@ -436,46 +474,39 @@ int fme_nn_copy_state_device(fme_ctx* c, uint32_t* d_out12, void* stream) {
 
 // perm holds one region per PU class, each as long as the context's job capacity (k_front writes
 // class c's jobs from c * capacity on, whatever the batch's class totals turn out to be): 96 bytes
-// per job of capacity, 83 MB for a 1080p frame's 862,920 jobs.
-static int ensure_work(fme_ctx* c, int n) {
+// per job of capacity, 83 MB for a 1080p frame's 862,920 jobs; and that once per batch slot.
+// Both slots are sized together.  *grows (may be null): a buffer had to grow (freeing the old one
+// waits for the device, so no batch in flight loses a buffer it reads).
+static int ensure_work(fme_ctx* c, int n, bool* grows = nullptr) {
   const size_t nb = ((size_t)n + kJobsPerScanBlock - 1) / kJobsPerScanBlock;
   if ((size_t)n * kNumClasses > (size_t)INT32_MAX) return fail(FME_E_INVALID, "%d jobs in one batch", n);
-  HIP_TRY(c->cls.reserve(n));
-  HIP_TRY(c->perm.reserve((size_t)n * kNumClasses));
-  HIP_TRY(c->blk_agg.reserve(nb * 9));
-  HIP_TRY(c->blk_prefix.reserve(nb * 9));
-  HIP_TRY(c->koff.reserve(n));
+  if (grows) *grows = (size_t)n > c->cls[0].cap || (size_t)n > c->koff[0].cap;
+  for (int b = 0; b < kOvSlots; b++) {
+    HIP_TRY(c->cls[b].reserve(n));
+    HIP_TRY(c->perm[b].reserve((size_t)n * kNumClasses));
+    HIP_TRY(c->blk_agg[b].reserve(nb * 9));
+    HIP_TRY(c->blk_prefix[b].reserve(nb * 9));
+    HIP_TRY(c->koff[b].reserve(n));
+  }
   return FME_OK;
 }
 
-// Before a batch's k_front: the counter block it counts in is zero.  In steady state the
-// previous batch's k_front left it so; otherwise both blocks are filled here.  The blocks stay
-// marked dirty until the caller has enqueued every launch of the batch (counts_done).
-static int counts_begin(fme_ctx* c, hipStream_t s) {
-  if (c->counts_dirty) HIP_TRY(hipMemsetAsync(c->counts.p, 0, 2 * kCountWords * sizeof(int32_t), s));
-  c->counts_dirty = true;
-  return FME_OK;
-}
-// A refinement batch fully enqueued: its k_front zeroes the other block, which the next batch uses.
-static void counts_done(fme_ctx* c) {
-  c->counts_cur ^= 1;
-  c->counts_dirty = false;
-}
-
-static WorkBufs work_bufs(fme_ctx* c) {
+// The work buffers of slot `slot`, counting in counter block `block`; the front end's last
+// workgroup zeroes block `zeroed`.
+static WorkBufs work_bufs(fme_ctx* c, int slot, int block, int zeroed) {
   WorkBufs w{};
-  w.cls = c->cls.p;
-  w.perm = c->perm.p;
-  w.perm_cap = (int32_t)(c->perm.cap / kNumClasses);
-  w.koff = c->koff.p;
-  w.counts = c->counts.p + c->counts_cur * kCountWords;
-  w.counts_next = c->counts.p + (c->counts_cur ^ 1) * kCountWords;
+  w.cls = c->cls[slot].p;
+  w.perm = c->perm[slot].p;
+  w.perm_cap = (int32_t)(c->perm[slot].cap / kNumClasses);
+  w.koff = c->koff[slot].p;
+  w.counts = c->counts.p + block * kCountWords;
+  w.counts_next = c->counts.p + zeroed * kCountWords;
   w.cursor = w.counts + kCursorWord;
   w.tile_ctr = w.counts + kTileCtrWord;
-  w.blk_agg = c->blk_agg.p;
-  w.blk_prefix = c->blk_prefix.p;
+  w.blk_agg = c->blk_agg[slot].p;
+  w.blk_prefix = c->blk_prefix[slot].p;
   w.nn_state = c->nn_state.p;
-  w.sched = c->d_sched.p;
+  w.sched = c->d_sched.p + slot;
   w.mv_out = nullptr;
   return w;
 }
@@ -497,12 +528,18 @@ BatchArgs fme::batch_args(const fme_ctx* c, const fme_job* jobs, int n) {
 // The picture / lambda tables go to the device in stream order as the argument of a one-block
 // kernel: rebinding pictures for the next frame never waits for the batch in flight, and the
 // batch stream holds no copy-engine transfer (which would queue behind bulk uploads).
-int fme::sync_tables(fme_ctx* c, hipStream_t s) {
+// Slot `slot`'s copy is brought up to date when the host tables changed since its last upload (a
+// batch's slot: its previous user is over before this launch, refine_batch's slot wait).
+static int put_tables(fme_ctx* c, int slot, hipStream_t s) {
   note_stream(c, s);   // every batch entry point passes here with its stream
   // a resident server could hold up this work on a hardware queue its stream shares: stop it
   // (a few microseconds; the next single call relaunches it)
   FME_TRY(srv_stop(c));
-  if (!c->tables_dirty) return FME_OK;
+  if (c->tables_dirty) {
+    c->tab_gen++;
+    c->tables_dirty = false;
+  }
+  if (c->slot_gen[slot] == c->tab_gen) return FME_OK;
   if (!c->h_tab) {
     void* p = nullptr;
     HIP_TRY(hipHostMalloc(&p, fme_ctx::kTabSlots * sizeof(TablesSlot), hipHostMallocMapped));
@@ -517,14 +554,46 @@ int fme::sync_tables(fme_ctx* c, hipStream_t s) {
   if (c->tab_used[k]) HIP_TRY(hipEventSynchronize(c->tab_ev[k]));   // its last launch has run
   std::memcpy(c->h_tab[k].pics, c->pics, sizeof(c->pics));
   std::memcpy(c->h_tab[k].ml, c->mlambda, sizeof(c->mlambda));
-  HIP_TRY(launch_put_tables(c->d_pics.p, c->d_mlambda.p, c->h_tab_dev + k, s));
+  HIP_TRY(launch_put_tables(c->d_pics.p + slot * FME_MAX_PICTURES, c->d_mlambda.p + slot * FME_MAX_LAMBDAS,
+                            c->h_tab_dev + k, s));
   HIP_TRY(hipEventRecord(c->tab_ev[k], s));
   c->tab_used[k] = true;
-  c->tables_dirty = false;
+  c->slot_gen[slot] = c->tab_gen;
   return FME_OK;
 }
 
-// Applies a reset / set of the NN state requested since the last batch, in stream order.
+int fme::sync_tables(fme_ctx* c, hipStream_t s) {
+  FME_TRY(wait_batches(c, s));
+  return put_tables(c, 0, s);
+}
+
+// What a planned batch (or integer search) does before its first launch: its end event, the waits
+// of its plan, and the fill of the counter blocks when they are in doubt.
+static int batch_begin(fme_ctx* c, const OverlapPlan& plan, hipStream_t s, hipEvent_t* done) {
+  hipEvent_t const prev_done = done_event(c, 1), slot_done = done_event(c, 2);
+  // this batch's end event: recorded once per use; before an entry of the ring is recorded again,
+  // the waits queued on its last record (by the two batches after that one) have been passed,
+  // which the end of the later of the two says
+  *done = c->done_ev[c->ov.seq % fme_ctx::kDoneRing];
+  if (c->ov.seq >= fme_ctx::kDoneRing)
+    HIP_TRY(hipEventSynchronize(c->done_ev[(c->ov.seq + 2) % fme_ctx::kDoneRing]));
+  if (plan.wait_prev_front) HIP_TRY(hipStreamWaitEvent(s, prev_done, 0));
+  if (plan.wait_slot) HIP_TRY(hipStreamWaitEvent(s, slot_done, 0));
+  // The counter block is zero: batch k - 2's k_front left it so (the first batches' blocks
+  // fme_create zeroed).  After a batch that was abandoned on the host half-way all blocks are
+  // filled here.  Its launches carry no end event, so the host waits for the context's streams
+  // first (an error path); the batch after this one waits for this one's end (kOvFill), so it does
+  // not start under the fill.
+  if (plan.fill_blocks) {
+    FME_TRY(drain_ctx(c));
+    HIP_TRY(hipMemsetAsync(c->counts.p, 0, kOvBlocks * kCountWords * sizeof(int32_t), s));
+  }
+  return FME_OK;
+}
+
+// Applies a reset / set of the NN state requested since the last batch, in stream order (before the
+// batch's tail, once the stream has waited for the previous batch's tail: that tail writes the
+// words this sets).
 static int apply_pending_state(fme_ctx* c, hipStream_t s) {
   if (!c->state_pending) return FME_OK;
   HIP_TRY(launch_put_state(c->nn_state.p + 12 * c->state_cur, c->pending_state, s));
@@ -576,19 +645,31 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
   if (c->cfg.nn_mode == 2 && c->nn_logits && n > c->nn_logits_cap)
     return fail(FME_E_INVALID, "fme_refine: %d jobs but the logit output holds %d", n, c->nn_logits_cap);
   HIP_TRY(hipSetDevice(c->device));
-  FME_TRY(ensure_work(c, n));
-  FME_TRY(sync_tables(c, s));
-  FME_TRY(apply_pending_state(c, s));
+  bool grows = false;
+  FME_TRY(ensure_work(c, n, &grows));
+  // The plan (fme_overlap_host.h): this batch's slot and counter block, and what its stream waits
+  // for.  Nothing on the device waits for another batch: every dependency is a stream wait on an
+  // earlier batch's end event.
+  const uint32_t features = (c->keys_fresh ? kOvKeys : 0u) | (c->cfg.nn_mode == 2 ? kOvDeepNn : 0u) |
+                            (c->cfg.bit_depth > 8 && c->main10_px ? kOvPx : 0u) |
+                            (d_jobs && d_jobs == c->d_jobs.p ? kOvStaged : 0u) | (grows ? kOvGrow : 0u);
+  const OverlapPlan plan = overlap_plan(c->ov, s, features);
+  hipEvent_t const prev_done = done_event(c, 1);
+  hipEvent_t done = nullptr;
+  FME_TRY(batch_begin(c, plan, s, &done));
+  FME_TRY(put_tables(c, plan.slot, s));
 
   BatchArgs a = batch_args(c, d_jobs, n);
+  a.pics = c->d_pics.p + plan.slot * FME_MAX_PICTURES;
+  a.mlambda = c->d_mlambda.p + plan.slot * FME_MAX_LAMBDAS;
   a.pjobs = d_jobs ? nullptr : d_pjobs;
   a.key_base = d_key_base;
-  a.koff = c->koff.p;
+  a.koff = c->koff[plan.slot].p;
   a.res = d_res;
   a.nn_mode = c->cfg.nn_mode ? 1 : 0;
   a.nn_in = c->nn_in;
   a.nn_in_cap = c->nn_in_cap;
-  WorkBufs w = work_bufs(c);
+  WorkBufs w = work_bufs(c, plan.slot, plan.block, plan.block_zeroed);
   w.mv_out = d_mv;
 
   const bool prof = c->profiling;
@@ -604,7 +685,9 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
     ev = c->ev[eb];
     HIP_TRY(hipEventRecord(ev[0], s));
   }
-  FME_TRY(counts_begin(c, s));
+  // the counter block is zero (batch_begin); the blocks stay in doubt until every launch of the
+  // batch is enqueued (overlap_commit)
+  overlap_begin(c->ov);
   HIP_TRY(launch_front(a, w, c->sched_p, s));
   if (prof) HIP_TRY(hipEventRecord(ev[3], s));
   if (c->ev_search) HIP_TRY(hipEventRecord(c->ev_search, s));
@@ -622,6 +705,18 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
     HIP_TRY(launch_search_lane(a, w, c->search_reserve, s));
   }
   if (prof) HIP_TRY(hipEventRecord(ev[4], s));
+  // the tails hand the NN state on: this one runs after the previous batch's, the one dependency
+  // between consecutive batches; a reset / set of the state belongs between the two
+  if (plan.wait_prev_tail) HIP_TRY(hipStreamWaitEvent(s, prev_done, 0));
+  if (c->state_read_last) {   // a copy of the state the previous tail left (fme_nn_copy_state_device) comes first
+    if (c->state_read_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->state_read_last, 0));
+    c->state_read_last = nullptr;
+  }
+  FME_TRY(apply_pending_state(c, s));
+  // (The tail stays on the batch's stream.  Where it becomes runnable a few microseconds after the
+  // next batch's search, that search's persistent workgroups hold every wave slot and the tail runs
+  // as they drain; on a stream of the highest priority it did the same, since resident workgroups
+  // are not displaced: DESIGN.md section 5 "Batch overlap".)
   if (prof) HIP_TRY(hipEventRecord(ev[5], s));
   HIP_TRY(c->cfg.nn_mode == 2
               ? launch_nn_deep_tail(c->net, c->d_net.p, c->nn_margin, c->nn_logits, a, w, c->state_cur, c->nn_engine, s)
@@ -630,8 +725,11 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
     HIP_TRY(hipEventRecord(ev[6], s));
     c->ev_head++;
   }
-  HIP_TRY(hipEventRecord(c->ev_done, s));
-  counts_done(c);
+  HIP_TRY(hipEventRecord(done, s));
+  c->ev_done = done;
+  c->last_slot = plan.slot;
+  c->keys_fresh = false;
+  overlap_commit(c->ov, s, features, plan);
   c->batch_issued = true;
   if (a.nn_mode) c->state_cur ^= 1;
   return FME_OK;
@@ -639,10 +737,22 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
 
 // After a refinement batch: the rejected-job count comes down, one synchronisation, FME_E_INVALID if any.
 int fme::check_rejected(fme_ctx* c, hipStream_t s, const char* name, const char* what) {
-  HIP_TRY(hipMemcpyAsync(c->h_counts, &c->d_sched.p->invalid, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(c->h_counts, &c->d_sched.p[c->last_slot].invalid, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (c->h_counts[0] > 0)
     return fail(FME_E_INVALID, "%s: %d job(s) %s", name, c->h_counts[0], what);
+  return FME_OK;
+}
+
+// The *_mv_* device entry points' full records (the search writes them, the tail reads them): context
+// scratch, one buffer per batch slot (the next batch's slot: refine_batch follows at once and plans
+// the same batch number).  The host-array entry points and the producers pass c->d_res whichever
+// slot their batch has: they are serialised before and after (kOvStaged), so no batch beside them
+// uses it.
+static int slot_records(fme_ctx* c, int n, fme_result** out) {
+  DevBuf<fme_result>& b = c->ov.seq % kOvSlots ? c->d_res1 : c->d_res;
+  HIP_TRY(b.reserve(n));
+  *out = b.p;
   return FME_OK;
 }
 
@@ -660,8 +770,9 @@ int fme_refine_mv_device(fme_ctx* c, const fme_job* d_jobs, fme_mv_result* d_out
   if (n < 0) return fail(FME_E_INVALID, "fme_refine_mv_device: n = %d", n);
   if (n == 0) return FME_OK;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(c->d_res.reserve(n));   // full records: context scratch
-  return refine_batch(c, d_jobs, c->d_res.p, d_out, n, static_cast<hipStream_t>(stream));
+  fme_result* d_res = nullptr;
+  FME_TRY(slot_records(c, n, &d_res));
+  return refine_batch(c, d_jobs, d_res, d_out, n, static_cast<hipStream_t>(stream));
 }
 
 // ---- packed jobs (include/fme.h fme_job_packed) -----------------------------------------------
@@ -751,10 +862,7 @@ static int refine_packed(fme_ctx* c, const fme_job_packed* d_jobs, const int32_t
   if (n < 0) return fail(FME_E_INVALID, "%s: n = %d", fn, n);
   if (n == 0) return FME_OK;
   HIP_TRY(hipSetDevice(c->device));
-  if (!d_res) {
-    HIP_TRY(c->d_res.reserve(n));   // full records: context scratch
-    d_res = c->d_res.p;
-  }
+  if (!d_res) FME_TRY(slot_records(c, n, &d_res));
   return refine_batch(c, nullptr, d_res, d_mv, n, static_cast<hipStream_t>(stream), d_jobs, d_key_base);
 }
 
@@ -916,7 +1024,7 @@ int fme_refine_status(fme_ctx* c) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipEventSynchronize(c->ev_done));
   int32_t v = 0;
-  HIP_TRY(hipMemcpy(&v, &c->d_sched.p->invalid, sizeof(v), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&v, &c->d_sched.p[c->last_slot].invalid, sizeof(v), hipMemcpyDeviceToHost));
   return v;
 }
 
@@ -928,14 +1036,14 @@ int fme_refine_status(fme_ctx* c) {
 int fme_debug_front(fme_ctx* c, int32_t* perm_out, long long perm_words, int32_t* sched_out, int sched_words,
                     int32_t* cap_out) {
   if (!c || !c->batch_issued) return fail(FME_E_STATE, "fme_debug_front: no batch issued");
-  if (perm_words < 0 || (size_t)perm_words > c->perm.cap || sched_words < 0 ||
+  if (perm_words < 0 || (size_t)perm_words > c->perm[c->last_slot].cap || sched_words < 0 ||
       (size_t)sched_words * sizeof(int32_t) > sizeof(Schedule))
     return fail(FME_E_INVALID, "fme_debug_front: length");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipEventSynchronize(c->ev_done));
-  if (perm_out && perm_words) HIP_TRY(hipMemcpy(perm_out, c->perm.p, (size_t)perm_words * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (sched_out && sched_words) HIP_TRY(hipMemcpy(sched_out, c->d_sched.p, (size_t)sched_words * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (cap_out) *cap_out = (int32_t)(c->perm.cap / kNumClasses);
+  if (perm_out && perm_words) HIP_TRY(hipMemcpy(perm_out, c->perm[c->last_slot].p, (size_t)perm_words * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (sched_out && sched_words) HIP_TRY(hipMemcpy(sched_out, c->d_sched.p + c->last_slot, (size_t)sched_words * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (cap_out) *cap_out = (int32_t)(c->perm[c->last_slot].cap / kNumClasses);
   return FME_OK;
 }
 
@@ -959,16 +1067,22 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   BatchArgs a = batch_args(c, d_jobs, n);
   a.nn_in = c->nn_in;   // FME_JOB_NN_IN jobs (the B producer's bi rounds) pass k_classify with their rows
   a.nn_in_cap = c->nn_in_cap;
-  WorkBufs w = work_bufs(c);
+  // The integer search is planned like a refinement batch (kOvForeign): behind every batch in
+  // flight, with a batch number of its own, so that its slot and counter block are nobody else's,
+  // the block comes round zeroed again (its scatter zeroes the block of the batch after next, as
+  // k_front does) and the batches after it wait for its end event.  It reads slot 0's tables.
+  const OverlapPlan plan = overlap_plan(c->ov, s, kOvForeign);
+  hipEvent_t done = nullptr;
+  FME_TRY(batch_begin(c, plan, s, &done));
+  WorkBufs w = work_bufs(c, plan.slot, plan.block, plan.block_zeroed);
   if (c->profiling) {
     if (!c->ev_tz[0]) {
       HIP_TRY(hipEventCreate(&c->ev_tz[0]));
       HIP_TRY(hipEventCreate(&c->ev_tz[1]));
     }
   }
-  // the integer search fills its counter block itself and leaves both marked dirty (counts_begin)
-  c->counts_dirty = true;
-  HIP_TRY(hipMemsetAsync(w.counts, 0, kCountWords * sizeof(int32_t), s));
+  // in doubt until everything is enqueued (an invalid job ends the call after the first pass)
+  overlap_begin(c->ov);
   HIP_TRY(launch_classify(a, w, s));
   HIP_TRY(hipMemcpyAsync(c->h_counts, w.counts, kCountWords * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -990,7 +1104,7 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   HIP_TRY(launch_scatter(a, w, c->sched_p, s));   // with its own class offsets (the schedule goes unused)
   TzArgs ta{};
   ta.a = a;
-  ta.perm = c->perm.p;
+  ta.perm = w.perm;
   ta.jobs_out = d_jobs;
   ta.ext = d_ext;
   ta.ext_stride = ext_stride;
@@ -1057,6 +1171,8 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   HIP_TRY(hipStreamWaitEvent(s, c->ev_join2, 0));
   if (c->profiling) HIP_TRY(hipEventRecord(c->ev_tz[1], s));
   c->tz_timed = c->profiling;
+  HIP_TRY(hipEventRecord(done, s));
+  overlap_commit(c->ov, s, kOvForeign, plan);
   return FME_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "fme_device.h"
+#include "fme_overlap_host.h"
 
 namespace fme {
 
@@ -93,8 +94,13 @@ struct fme_ctx {
   bool lambda_set[FME_MAX_LAMBDAS]{};
   bool tables_dirty = true;
 
+  // The device tables, one copy per batch slot (fme_overlap_host.h): slot b's at d_pics.p +
+  // b * FME_MAX_PICTURES and d_mlambda.p + b * FME_MAX_LAMBDAS.  Everything but the refinement
+  // batches reads slot 0 (sync_tables).  tab_gen counts the host tables' changes, slot_gen[b] is
+  // the change slot b holds.
   fme::DevBuf<fme::PicDesc> d_pics;
   fme::DevBuf<double> d_mlambda;
+  unsigned long long tab_gen = 1, slot_gen[fme::kOvSlots] = {};
   // the tables' upload ring (sync_tables): pinned, device-mapped slots, each guarded by the event of
   // the launch that reads it
   static constexpr int kTabSlots = 16;
@@ -121,20 +127,32 @@ struct fme_ctx {
 
   fme::DevBuf<fme_job> d_jobs;      // staging for fme_refine (host arrays)
   fme::DevBuf<fme_result> d_res;
+  fme::DevBuf<fme_result> d_res1;    // the *_mv_* device entry points' records of a batch in slot 1
   fme::DevBuf<fme_mv_result> d_mv;   // staging for fme_refine_mv
-  fme::DevBuf<int32_t> koff;         // packed batches: key offset per keyed job (k_classify)
-  fme::DevBuf<uint8_t> cls;
-  fme::DevBuf<int32_t> perm;
-  fme::DevBuf<int32_t> counts;      // two counter blocks (kCountWords each), used by alternate batches
-  int counts_cur = 0;          // the block the next batch counts in (zero unless counts_dirty)
-  bool counts_dirty = false;   // the blocks are not known to be zero: the next batch fills both
-  fme::DevBuf<int32_t> blk_agg;
-  fme::DevBuf<int32_t> blk_prefix;
+  // What a batch's kernels hand each other, one set per batch slot (consecutive batches on two
+  // streams overlap: fme_overlap_host.h); the integer search takes a batch number and its slot.
+  fme::DevBuf<int32_t> koff[fme::kOvSlots];   // packed batches: key offset per keyed job (k_classify)
+  fme::DevBuf<uint8_t> cls[fme::kOvSlots];
+  fme::DevBuf<int32_t> perm[fme::kOvSlots];
+  fme::DevBuf<int32_t> blk_agg[fme::kOvSlots];
+  fme::DevBuf<int32_t> blk_prefix[fme::kOvSlots];
+  fme::DevBuf<int32_t> counts;      // kOvBlocks counter blocks (kCountWords each), used in rotation
+  fme::OverlapState ov;             // batch count, the last two batches' streams, blocks in doubt
+  // the batches' end events: batch k records done_ev[k % kDoneRing] once, after its tail
+  static constexpr int kDoneRing = 16;
+  hipEvent_t done_ev[kDoneRing] = {};
+  // fme_nn_copy_state_device's reads of the carried state: the next batch's set / reset waits for the latest
+  hipEvent_t state_read_ev[kDoneRing] = {};
+  long long state_reads = 0;
+  hipEvent_t state_read_last = nullptr;
+  hipStream_t state_read_stream = nullptr;
+  int last_slot = 0;                // slot of the last batch (fme_refine_status, fme_debug_front)
+  bool keys_fresh = false;          // the key buffer was written since the last batch
   fme::DevBuf<uint32_t> nn_state;   // 2 x 12 words
   int state_cur = 0;
   bool state_pending = false;   // reset / set_state not yet applied (next batch, stream order)
   uint32_t pending_state[12] = {};
-  fme::DevBuf<fme::Schedule> d_sched;     // built by k_scatter each batch
+  fme::DevBuf<fme::Schedule> d_sched;     // [kOvSlots], built by k_front each batch
   fme::SchedParams sched_p{};
   int32_t* h_counts = nullptr; // pinned
 
@@ -256,7 +274,7 @@ struct fme_ctx {
   long long ev_head = 0;        // sets recorded
   long long ev_tail = 0;        // sets harvested
   bool timed = false;
-  hipEvent_t ev_done = nullptr; // end of the last batch (fme_refine_status)
+  hipEvent_t ev_done = nullptr; // end of the last batch: one of done_ev (fme_refine_status)
   hipEvent_t ev_search = nullptr; // caller's event, recorded before each search launch (fme_set_search_event)
   int search_reserve = 0;         // resident search workgroups left free (fme_set_search_reserve)
   bool main10_px = false;         // bit depth 10: the pixel kernel instead of the lane kernel
@@ -282,8 +300,10 @@ hipError_t launch_nn_deep_single(const fme_nn_net& n, const void* packed, const 
                                  uint32_t* flag, uint32_t seq, hipStream_t s);
 
 // The runtime functions the producers call (fme_api.cpp, documented there).
+// what every entry point but a refinement batch calls first: s waits for the refinement batches in
+// flight on other streams, then slot 0's tables are brought up to date in stream order
 int sync_tables(fme_ctx* c, hipStream_t s);
-int grow_keys(fme_ctx* c, size_t n);
+int grow_keys(fme_ctx* c, size_t n);   // called before the key buffer is written: the next batch serialises
 BatchArgs batch_args(const fme_ctx* c, const fme_job* jobs, int n);   // the fields every batch shares
 int refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_result* d_mv, int n, hipStream_t s,
                  const fme_job_packed* d_pjobs = nullptr, const int32_t* d_key_base = nullptr);

@@ -158,7 +158,7 @@ class FrameReplay:
     def __init__(self, ctx, base_jobs, pool, lambda_of, n_steps, frames_per_step=1, world=1, rank=0, device=None,
                  group=None, defer_download=True, key_reqs=None, key_count=0, nn_rows=None,
                  download_engine="sdma", download_wgs=8, search_reserve=0, packed=True, copy_streams=1, slots=3,
-                 max_ahead=4, precreate_events=True, warm_engines=True, timeline=False):
+                 max_ahead=4, precreate_events=True, warm_engines=True, timeline=False, compute_streams=2):
         """ctx: an FmeContext on `device`; base_jobs: one frame's jobs (ref_id = reference
         distance - 1); pool: uint8 [P, H, W] host frames, frame g's pictures are pool[g % P];
         lambda_of(g): frame g's lambda (pool uint16: main10 samples for a bit-depth-10 context,
@@ -183,7 +183,11 @@ class FrameReplay:
         no CUs), "kernel" (fme_download_device: the library's copy kernel of download_wgs workgroups
         of 256 lanes) or "blit" (hipMemcpyAsync, which this ROCm runs as a blit kernel of hundreds of
         workgroups that take the search kernel's CUs).  search_reserve: resident search workgroups
-        left free (fme_set_search_reserve), so the download kernel runs beside the search."""
+        left free (fme_set_search_reserve), so the download kernel runs beside the search.
+        compute_streams: 2 (default) runs step k's batch on compute stream k % 2 (the device's
+        default stream and one more), so that the library lets consecutive batches overlap: step
+        k+1's front end and search do not wait for step k's NN tail, only the tails wait for each
+        other.  1 keeps every batch on the default stream, in series (kernel-alone profiling)."""
         import torch
         from .abi import JOB_PACKED_DTYPE
         from .runtime import FmeError, pack_jobs
@@ -240,6 +244,11 @@ class FrameReplay:
         self.org = torch.empty((n_steps * F, H, W), dtype=pdt, device=device)
         self.states = torch.zeros((n_steps, 12), dtype=torch.int32, device=device)
         self.s_comp = torch.cuda.default_stream(device)
+        if compute_streams not in (1, 2):
+            raise ValueError("compute_streams 1 or 2")
+        self.compute_streams = compute_streams
+        # step k's batch runs on s_comps[k % compute_streams]
+        self.s_comps = [self.s_comp] + [torch.cuda.Stream(device) for _ in range(compute_streams - 1)]
         self.s_copy = torch.cuda.Stream(device)   # H2D: jobs, originals, reconstructions (+ D2H: copy_streams 1)
         if copy_streams not in (1, 2):
             raise ValueError("copy_streams 1 or 2")
@@ -306,9 +315,15 @@ class FrameReplay:
             self.ctx.set_search_event(None)
         except Exception:
             pass
+        for sc in self.s_comps:   # nothing queued may still record into an event destroyed below
+            sc.synchronize()
         for e in self.ev_search:
             e.destroy()
         self.ev_search = []
+
+    def comp_stream(self, k):
+        """The compute stream of step k's batch."""
+        return self.s_comps[k % len(self.s_comps)]
 
     def first_frame(self, k):
         """First frame of this rank's step k."""
@@ -436,11 +451,13 @@ class FrameReplay:
             ctx.bind_picture_device(s, self.recon[f0 - REFS + s + REFS].data_ptr(), W, W, H)
 
     # -- one step -----------------------------------------------------------------------------
-    # Streams: the batch runs on the device's default stream; every copy runs on one copy stream,
+    # Streams: step k's batch runs on compute stream k % 2 (the device's default stream and one more:
+    # the library overlaps consecutive batches on different streams); every copy runs on one copy stream,
     # in series, as issue(k) queues them: the H2D of step k+1 (jobs, key bases, originals, the
     # published reconstruction; its slot was last read by step k+1-R), then the D2H of step k-1's
     # results, which waits until step k's search kernel runs (the library records ev_search right
-    # before each search launch).  In series the two directions take 0.93 ms per 1080p step with
+    # before each search launch) and step k-1's batch has ended (with two compute streams step k's
+    # search no longer waits for step k-1's tail).  In series the two directions take 0.93 ms per 1080p step with
     # 32-byte jobs (H2D 0.68 + D2H 0.25 ms, gpurun_out/d2h.log), less than the batch; in flight
     # together on two streams they took 2.57 ms, which is what bound round 5's pipeline.  The
     # download starting only once the search runs keeps a device-to-host copy's posted PCIe writes
@@ -489,7 +506,7 @@ class FrameReplay:
         if self.uploaded < k:
             self._upload(k)
         t.append(pc())
-        comp = self.s_comp
+        comp = self.comp_stream(k)
         comp.wait_event(self.ev_in[k])
         if k >= self.R:
             comp.wait_event(self.ev_out[k - self.R])       # step k-R's results have left the slot
@@ -518,8 +535,8 @@ class FrameReplay:
         if not self.defer_download:
             self._download(k, self.ev_comp[k])
         else:
-            if self.pending is not None:   # step k's search started: k-1 is done (its own batch event otherwise)
-                self._download(self.pending, self.ev_search[k] if self.n > 0 else self.ev_comp[self.pending])
+            if self.pending is not None:   # step k's search started and step k-1's batch is over
+                self._download(self.pending, self.ev_search[k] if self.n > 0 else None)
             self.pending = k
         t.append(pc())
         self.host_ms.append((t[-1] - t[0]) * 1e3)
@@ -539,8 +556,10 @@ class FrameReplay:
         dn = self.s_down
         if isinstance(after, _RawEvent):
             after.wait(dn)
-        else:
+        elif after is not None:
             dn.wait_event(after)
+        if after is not self.ev_comp[k]:   # a search event of step k+1 does not say that step k's tail is over
+            dn.wait_event(self.ev_comp[k])
         if self.tl:
             self.tl["d0"][k].record(dn)
         self._copy_down(k, dn)
@@ -555,7 +574,8 @@ class FrameReplay:
             self._download(self.pending, self.ev_comp[self.pending])
             self.pending = None
         self.s_copy.synchronize()
-        self.s_comp.synchronize()
+        for sc in self.s_comps:
+            sc.synchronize()
         self.s_down.synchronize()
         self.ctx.set_search_event(None)
 
@@ -597,7 +617,7 @@ class FrameReplay:
                       for k in range(k0, k1)}
 
     def _resident_batch(self, k, n):
-        ctx, comp = self.ctx, self.s_comp
+        ctx, comp = self.ctx, self.comp_stream(k)
         b = k % self.R
         self._bind(k)
         if self.kreqs is not None:   # this step's keys, built on the device from its pictures
@@ -607,7 +627,7 @@ class FrameReplay:
 
     def issue_resident(self, k):
         """Step k from HBM-resident inputs into r_out[k] (no copy, no host wait)."""
-        ctx, comp = self.ctx, self.s_comp
+        ctx, comp = self.ctx, self.comp_stream(k)
         ctx.set_search_event(None)
         if self.world > 1:
             ctx.nn_reset()                                 # stream-ordered: this batch starts fresh
@@ -623,7 +643,8 @@ class FrameReplay:
             return 0
         import torch.distributed as dist
         torch = self.torch
-        self.s_comp.synchronize()
+        for sc in self.s_comps:
+            sc.synchronize()
         st = self.states if dist.get_backend(self.group) != "gloo" else self.states.cpu()
         gathered = [torch.zeros_like(st) for _ in range(self.world)]
         dist.all_gather(gathered, st, group=self.group)

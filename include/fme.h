@@ -316,8 +316,30 @@ int fme_nn_copy_state_device(fme_ctx* ctx, uint32_t* d_out12, void* stream);
  * run; NULL turns it off.  A pipeline waits on it to start the previous batch's results download
  * only when the long search kernel is running: a device-to-host copy's posted PCIe writes hold
  * back every read the device issues behind them (AQL packet and kernel-argument fetches), so a
- * download overlapping a prologue delayed each of its launches by the length of the copy.   */
+ * download overlapping a prologue delayed each of its launches by the length of the copy.
+ * The event does not say that the previous batch has ended: where consecutive batches are issued
+ * on two streams (below), this batch's search starts before the previous batch's tail has run, so
+ * a download of the previous batch's results waits for that batch's own end as well.          */
 int fme_set_search_event(fme_ctx* ctx, void* event);
+
+/* Overlapping consecutive batches.  The fme_refine*_device entry points may be called for batch
+ * k+1 on another stream than batch k while batch k is still running: issue the batches on two
+ * streams in turn.  The context then keeps two sets of work buffers (twice the memory: 192 bytes
+ * per job of capacity) and orders the batches with stream waits on its own events: batch k+1's
+ * front end and search do not wait for batch k, only its NN tail waits for batch k's tail (the
+ * carried NN_pred state), and batch k+2 waits for batch k's end.  Results are those of the same
+ * calls on one stream, bit for bit.  fme_nn_set_state / fme_nn_reset_state between two such
+ * calls take effect between the two tails.  A batch waits for every batch in flight first when
+ * the key buffer was written since the last batch (fme_set_keys, fme_build_bipred_keys*), with
+ * nn_mode 2, with FME_MAIN10_SEARCH=px, through the host-array entry points and the producers,
+ * and when a work buffer grows; so does the batch after it.  The integer search is ordered like
+ * such a batch, in both directions.  fme_nn_copy_state_device waits on its stream for the
+ * batches in flight, and the next batch's state set / reset waits for the copy.  Every other entry
+ * point called with a stream (motion compensation, prediction error, skip check, cost surface,
+ * key building, the producers) waits on it for the batches in flight, but no batch waits for
+ * them: issue such a call on the stream of the batch that follows it, or order the two yourself.
+ * The context's own events order nothing else: a caller's reads of a batch's output, and its
+ * writes of a batch's inputs, follow that batch's stream as before.                            */
 
 /* Workgroup slots the search kernel leaves free for a few-workgroup kernel on another stream (the
  * results download of fme_download_device, queued beside the next batch's search): 0 (default)

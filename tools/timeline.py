@@ -33,6 +33,20 @@ def main():
         return
     gaps = [(cls[i + 1][0] - cls[i][0]) / 1e3 for i in range(len(cls) - 1)]
     print("front-to-front (us):", [round(g) for g in gaps])
+    # batches may overlap (consecutive batches on two streams): per search, the idle time before the
+    # next search starts (negative: they run side by side), whether the next front end started
+    # while it ran, and when the tail that follows it ended against the next search's end
+    se = [e for e in ev if e[2] == "K" and "k_search_" in e[3]]
+    ta = [e for e in ev if e[2] == "K" and "k_nn_" in e[3] and "tail" in e[3]]
+    print("search end -> next search start (us):", [round((b[0] - a[1]) / 1e3, 1) for a, b in zip(se, se[1:])][-show - 8:])
+    early = sum(1 for f in cls if any(a[0] < f[0] < a[1] for a in se))
+    print(f"front ends that start while a search runs: {early} of {len(cls)}")
+    late = []
+    for a, b in zip(se, se[1:]):
+        t = next((x for x in ta if x[0] >= a[1]), None)   # the first tail that starts after this search ends
+        if t:
+            late.append(round((t[1] - b[1]) / 1e3, 1))
+    print("tail end - next search end (us; negative: the tail is over first):", late[-show - 8:])
     i0 = len(cls) - show - 1 if first is None else first
     t0 = cls[i0][0]
     t1 = cls[min(i0 + show, len(cls) - 1)][0]
