@@ -1060,6 +1060,20 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   if (!c || (n > 0 && (!d_jobs || !d_ext))) return fail(FME_E_INVALID, "fme_integer_search_device: null argument");
   if (n < 0) return fail(FME_E_INVALID, "fme_integer_search_device: n = %d", n);
   if (n == 0) return FME_OK;
+  // The search groups its PUs by (unit-shape kernel, reference picture, CTU) on the device, each
+  // group's search area read into LDS once (fme_tz.hip k_tz_staged): np groups per kernel, refused
+  // here, before anything is planned or enqueued, when the bound pictures make too many.
+  int cw = 0, ch = 0, npic = 0;   // CTU grid of the largest bound picture; reference ids < npic
+  for (int i = 0; i < FME_MAX_PICTURES; i++)
+    if (c->pics[i].luma) {
+      cw = std::max(cw, (c->pics[i].width + 63) / 64);
+      ch = std::max(ch, (c->pics[i].height + 63) / 64);
+      npic = i + 1;
+    }
+  const long long np = (long long)npic * cw * ch;   // 0: no picture bound, every job fails k_classify
+  if (np > kTzMaxPairs)
+    return fail(FME_E_UNSUPPORTED, "fme_integer_search_device: %lld (picture slot, CTU) pairs (%d slots x %d x %d CTUs), the limit is %lld",
+                np, npic, cw, ch, kTzMaxPairs);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   FME_TRY(ensure_work(c, n));
@@ -1090,17 +1104,6 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
     return fail(FME_E_INVALID, "fme_integer_search_device: %d job(s) with an unsupported PU size or unset picture/lambda/key",
                 c->h_counts[kNumClasses]);
   const bool keyed = c->h_counts[kKeyedWord] > 0;
-  TzSchedule sc{};
-  int off = 0, nb[3] = {0, 0, 0};
-  for (int k = 0; k < kNumClasses; k++) {
-    const int cnt = c->h_counts[k];
-    sc.class_off[k] = off;
-    sc.class_cnt[k] = cnt;
-    for (int q = 0; q < 3; q++) sc.prefix[q][k] = nb[q];
-    nb[tz_kernel_of(k)] += cnt;
-    off += cnt;
-  }
-  for (int q = 0; q < 3; q++) sc.prefix[q][kNumClasses] = nb[q];
   HIP_TRY(launch_scatter(a, w, c->sched_p, s));   // with its own class offsets (the schedule goes unused)
   TzArgs ta{};
   ta.a = a;
@@ -1120,51 +1123,32 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
   if (!c->ev_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   if (!c->ev_join2) HIP_TRY(hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));
-  // the staged form (FME_TZ_STAGE): PUs grouped by (kernel, reference, CTU) on the device, each
-  // group's search area read into LDS once (fme_tz.hip k_tz_staged)
-  int cw = 0, ch = 0, npic = 0;   // CTU grid of the largest bound picture; reference ids < npic
-  for (int i = 0; i < FME_MAX_PICTURES; i++)
-    if (c->pics[i].luma) {
-      cw = std::max(cw, (c->pics[i].width + 63) / 64);
-      ch = std::max(ch, (c->pics[i].height + 63) / 64);
-      npic = i + 1;
-    }
-  const long long np = (long long)npic * cw * ch;
-  const bool stage = c->cfg.bit_depth == 8 || std::getenv("FME_TZ10_UNSTAGED") == nullptr;   // (A/B switch)
-  if (FME_TZ_STAGE && stage && np > 0 && np <= (1LL << 20)) {
-    const size_t words = 8 + 12 * (size_t)np;
-    if (c->d_tzp.cap < words || c->d_tzp_perm.cap < (size_t)n) {
-      FME_TRY(drain_ctx(c));   // no launch of an earlier call still reads the old buffers
-      HIP_TRY(c->d_tzp.reserve(words));
-      HIP_TRY(c->d_tzp_perm.reserve(n));
-    }
-    TzPairs tp{};
-    int32_t* b = c->d_tzp.p;
-    tp.nseg = b;
-    tp.cnt = b + 8;
-    tp.cursor = tp.cnt + 3 * np;
-    tp.off = tp.cursor + 3 * np;
-    tp.seg = tp.off + 3 * np;
-    tp.perm = c->d_tzp_perm.p;
-    tp.np = (int32_t)np;
-    tp.cw = cw;
-    tp.ch = ch;
-    HIP_TRY(hipMemsetAsync(b, 0, (8 + 3 * (size_t)np) * sizeof(int32_t), s));
-    HIP_TRY(launch_tz_pairs(ta, tp, w.cls, n, s));
-    HIP_TRY(hipEventRecord(c->ev_fork, s));
-    HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(c->aux2, c->ev_fork, 0));
-    HIP_TRY(launch_tz_staged(ta, tp, 0, keyed, c->cfg.bit_depth, c->aux));
-    HIP_TRY(launch_tz_staged(ta, tp, 1, keyed, c->cfg.bit_depth, c->aux2));
-    HIP_TRY(launch_tz_staged(ta, tp, 2, keyed, c->cfg.bit_depth, s));
-  } else {
-    HIP_TRY(hipEventRecord(c->ev_fork, s));
-    HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(c->aux2, c->ev_fork, 0));
-    HIP_TRY(launch_tz_wave(ta, sc, 0, keyed, c->cfg.bit_depth, c->aux));
-    HIP_TRY(launch_tz_wave(ta, sc, 1, keyed, c->cfg.bit_depth, c->aux2));
-    HIP_TRY(launch_tz_wave(ta, sc, 2, keyed, c->cfg.bit_depth, s));
+  // the groups (np > 0 here: a job that passed k_classify names a bound picture)
+  const size_t words = 8 + 12 * (size_t)np;
+  if (c->d_tzp.cap < words || c->d_tzp_perm.cap < (size_t)n) {
+    FME_TRY(drain_ctx(c));   // no launch of an earlier call still reads the old buffers
+    HIP_TRY(c->d_tzp.reserve(words));
+    HIP_TRY(c->d_tzp_perm.reserve(n));
   }
+  TzPairs tp{};
+  int32_t* b = c->d_tzp.p;
+  tp.nseg = b;
+  tp.cnt = b + 8;
+  tp.cursor = tp.cnt + 3 * np;
+  tp.off = tp.cursor + 3 * np;
+  tp.seg = tp.off + 3 * np;
+  tp.perm = c->d_tzp_perm.p;
+  tp.np = (int32_t)np;
+  tp.cw = cw;
+  tp.ch = ch;
+  HIP_TRY(hipMemsetAsync(b, 0, (8 + 3 * (size_t)np) * sizeof(int32_t), s));
+  HIP_TRY(launch_tz_pairs(ta, tp, w.cls, n, s));
+  HIP_TRY(hipEventRecord(c->ev_fork, s));
+  HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_fork, 0));
+  HIP_TRY(hipStreamWaitEvent(c->aux2, c->ev_fork, 0));
+  HIP_TRY(launch_tz_staged(ta, tp, 0, keyed, c->cfg.bit_depth, c->aux));
+  HIP_TRY(launch_tz_staged(ta, tp, 1, keyed, c->cfg.bit_depth, c->aux2));
+  HIP_TRY(launch_tz_staged(ta, tp, 2, keyed, c->cfg.bit_depth, s));
   HIP_TRY(hipEventRecord(c->ev_join, c->aux));
   HIP_TRY(hipEventRecord(c->ev_join2, c->aux2));
   HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));

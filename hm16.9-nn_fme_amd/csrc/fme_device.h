@@ -11,12 +11,6 @@
 #include "../../include/fme_surface.h"
 #include "fme_srv_pack.h"
 
-// 1: the bulk integer search stages each (kernel, reference, CTU) group's search area in LDS
-// (fme_tz.hip k_tz_staged); 0: one wave per PU straight from the class order (k_tz_wave)
-#ifndef FME_TZ_STAGE
-#define FME_TZ_STAGE 1
-#endif
-
 namespace fme {
 
 constexpr int kNumClasses = 24;      // HEVC inter PU shapes 4x8 .. 64x64 incl. AMP
@@ -278,19 +272,10 @@ __device__ __forceinline__ void tz_pred_at(const TzArgs& ta, int i, int k, int& 
   x = e->preds[k][0];
   y = e->preds[k][1];
 }
-int tz_kernel_of(int cls);    // 0: 4x8 units, 1: 8x4, 2: 8x8
-int tz_lanes_per_pu(int cls);
-// Host-built schedule of the integer-search kernels (passed by value).
-struct TzSchedule {
-  int32_t prefix[3][kNumClasses + 1];
-  int32_t class_off[kNumClasses];
-  int32_t class_cnt[kNumClasses];
-};
-// keyed: some job of the batch reads a key block (bi-pred): the kernels that hold int16 keys;
-// otherwise the uni-pred form, whose key rows take half the registers
-hipError_t launch_tz_wave(const TzArgs& ta, const TzSchedule& sc, int kid, bool keyed, int bit_depth, hipStream_t s);   // prefix in waves
-// The staged bulk search's groups (fme_tz.hip k_tz_staged): PUs by (unit-shape kernel kid,
-// reference picture, CTU), np = (bound picture ids) * cw * ch groups per kernel.
+// The bulk search's groups (fme_tz.hip k_tz_staged): PUs by (unit-shape kernel kid: 0 the 4x8
+// units, 1 the 8x4, 2 the 8x8; reference picture; CTU), np = (bound picture ids) * cw * ch groups
+// per kernel, at most kTzMaxPairs.
+constexpr long long kTzMaxPairs = 1LL << 20;
 struct TzPairs {
   int32_t* cnt;      // [3 np] PUs per group (zeroed before launch_tz_pairs)
   int32_t* cursor;   // [3 np]
@@ -301,6 +286,8 @@ struct TzPairs {
   int32_t np, cw, ch;
 };
 hipError_t launch_tz_pairs(const TzArgs& ta, const TzPairs& tp, const uint8_t* cls, int n, hipStream_t s);
+// keyed: some job of the batch reads a key block (bi-pred): the kernels that hold int16 keys;
+// otherwise the uni-pred form, whose key rows take half the registers
 hipError_t launch_tz_staged(const TzArgs& ta, const TzPairs& tp, int kid, bool keyed, int bit_depth, hipStream_t s);
 // The dependency levels of a producer's m_integerMv2Nx2N chain (fme_tz.hip k_tz_level): jobs in
 // level order, level l = jobs [lvl_off[l], lvl_off[l+1]), one launch per level, back to back.
@@ -315,7 +302,7 @@ hipError_t launch_tz_levels(const TzArgs& ta, const TzChain& ch, const int32_t* 
 // the NN writer maxima; the workgroup that finishes last writes *w.sched (block ranges, XCD queues,
 // invalid count) and w.blk_prefix and zeroes w.counts_next
 hipError_t launch_front(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, hipStream_t s);
-// The integer search's two passes (its class offsets are dense and its schedule is built on the host):
+// The integer search's two passes (its class offsets are dense):
 // validation, class and the class histogram in w.counts,
 hipError_t launch_classify(const BatchArgs& a, const WorkBufs& w, hipStream_t s);
 // then w.counts -> class offsets and the jobs grouped by class in perm[0, n) (block 0 also writes

@@ -10,17 +10,15 @@
 // xTZ2PointSearch (1191-1322), xSetSearchRange (4602-4624), TComDataCU::clipMv
 // (TComDataCU.cpp:2773-2786), TComMv::divideByPowerOf2 (TComMv.h:122-130).
 //
-// Mapping: one wave per PU (k_tz_wave; tz_wave below): the PU's units (8x8, 8x4 or 4x8; the group
-// of L lanes padded to a power of two) sit in consecutive lanes, and the wave's 64 / L groups
-// evaluate the candidates of one reference list (a diamond ring, the raster, ...) together.
+// Mapping: one wave per PU (k_tz_staged, k_tz_level; tz_wave below): the PU's units (8x8, 8x4 or
+// 4x8; the group of L lanes padded to a power of two) sit in consecutive lanes, and the wave's
+// 64 / L groups evaluate the candidates of one reference list (a diamond ring, the raster, ...)
+// together.
 // Metric (the NN_FME integer-ME setDistParam, TComRdCost.cpp:200-230): SSE for widths 4..64, SAD
 // for 12/24/48 with the FEN even-row subsampling when H > 8; uni-pred keys as (s - 128) bytes
 // (SSE = Sk2 - 2 Sks + Sss with v_dot4_i32_i8, SAD with v_sad_u8), bi-pred keys (2 org - pred,
 // int16) as packed pairs.
 #include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdio>
 
 #include "fme_device.h"
 #include "fme_simd.h"
@@ -39,10 +37,6 @@ __device__ unsigned long long g_tz_count[3][2];   // [kernel 4x8 / 8x4 / 8x8 uni
 namespace {
 using namespace simd;
 
-#ifndef FME_TZ_NT   // threads per workgroup of the bulk search (one wave per PU)
-#define FME_TZ_NT 256
-#endif
-constexpr int kTzNT = FME_TZ_NT;
 #define FME_AI __attribute__((always_inline))
 
 template <int CTRL>
@@ -428,36 +422,18 @@ __device__ __forceinline__ uint64_t wave_min_from(uint64_t key, int L, int lim) 
   return key;
 }
 
-// NW waves of one workgroup on one PU (the producer's chain levels: few jobs, latency-bound): the
-// groups of all waves share each list; wave minima meet in LDS.
-template <int NW>
-__device__ __forceinline__ uint64_t block_min(uint64_t key) {
-  if constexpr (NW == 1) {
-    return key;
-  } else {
-    __shared__ uint64_t s_key[NW];
-    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
-    __syncthreads();
-    uint64_t m = s_key[0];
-#pragma unroll
-    for (int w = 1; w < NW; w++) m = s_key[w] < m ? s_key[w] : m;
-    __syncthreads();
-    return m;
-  }
-}
-
 // KB: -1 any job; 0 the uni-pred form (no job of the launch reads a key block: the key rows are
 // UW / 4 dwords of bytes, half the registers of the int16 form)
-// BD: the luma bit depth (8, or 10: uint16 planes, the key as sample pairs, no staged tile).
-template <int UW, int UH, int NW = 1, int KB = -1, int BD = 8>
+// BD: the luma bit depth (8, or 10: uint16 planes, the key and the staged tile as sample pairs).
+template <int UW, int UH, int KB = -1, int BD = 8>
 __device__ __forceinline__ void tz_wave(const TzArgs& ta, int jid, const fme_job& j, int PW, int PH, int pred_x,
                                         int pred_y, const TileRef& tile = TileRef{nullptr, 0, 0}) {
   const BatchArgs& a = ta.a;
-  const int lane = (int)threadIdx.x & 63, wid = NW == 1 ? 0 : (int)threadIdx.x >> 6;
+  const int lane = (int)threadIdx.x & 63;
   const int UX = PW / UW, LR = UX * (PH / UH);
   int L = 1;
   while (L < LR) L <<= 1;
-  const int G = NW * (64 / L), g = wid * (64 / L) + lane / L, u = lane % L;
+  const int G = 64 / L, g = lane / L, u = lane % L;
   const bool real = u < LR;
   const int uu = real ? u : 0;
   const int ux = uu % UX, uy = uu / UX;
@@ -505,8 +481,8 @@ __device__ __forceinline__ void tz_wave(const TzArgs& ta, int jid, const fme_job
   // The backups' input path (FME_TZ_RING, Backups/4 and Backups/15 xTZSearch): every distortion
   // xTZSearchHelp computes is pushed into array_e (Backups/4:659, 677); C = the least of the pushes
   // before the final square (:4343-4348), and the square + ring pushes after it are the NN inputs.
-  // The bulk kernel only (one wave per PU: the slots are gathered with in-wave shuffles).
-  const bool ring = NW == 1 && ta.nn_in != nullptr && (e.flags & FME_TZ_RING) && !(j.flags & FME_JOB_BIPRED);
+  // (One wave per PU: the slots are gathered with in-wave shuffles.)
+  const bool ring = ta.nn_in != nullptr && (e.flags & FME_TZ_RING) && !(j.flags & FME_JOB_BIPRED);
   uint32_t cmin = 0xFFFFFFFFu;   // least distortion pushed so far (wave-uniform)
 
   // distortion + MV cost of this group's candidate (all lanes of the group get it); ~0: not tested.
@@ -567,7 +543,7 @@ __device__ __forceinline__ void tz_wave(const TzArgs& ta, int jid, const fme_job
       const bool v = i < n && pt(i, x, y);
       uint32_t dist;
       const uint32_t c = cost_at(x, y, v, dist);
-      const uint64_t key = block_min<NW>(wave_min_from(((uint64_t)c << 32) | (uint32_t)i, L, 64));
+      const uint64_t key = wave_min_from(((uint64_t)c << 32) | (uint32_t)i, L, 64);
       best = key < best ? key : best;
       push_min(dist, 64);
     }
@@ -646,23 +622,12 @@ __device__ __forceinline__ void tz_wave(const TzArgs& ta, int jid, const fme_job
         const bool v = i < NS && (i == 0 || i == 4 || (i == 5 && has_pred) || (i <= 3 && enh));
         uint32_t dist;
         const uint32_t c = cost_at(x, y, v, dist);
-        if constexpr (NW == 1) {
 #pragma unroll
-          for (int q = 0; q < NS; q++)
-            if (q >= base && q < base + G) {
-              cs[q] = __shfl(c, (q - base) * L, 64);
-              ds[q] = __shfl(dist, (q - base) * L, 64);
-            }
-        } else {   // several waves: the costs through LDS
-          __shared__ uint32_t s_cs[NS];
-          if (i < NS && u == 0) s_cs[i] = c;
-          __syncthreads();
-#pragma unroll
-          for (int q = 0; q < NS; q++)
-            if (q >= base && q < base + G) cs[q] = s_cs[q];
-          __syncthreads();
-          (void)dist;
-        }
+        for (int q = 0; q < NS; q++)
+          if (q >= base && q < base + G) {
+            cs[q] = __shfl(c, (q - base) * L, 64);
+            ds[q] = __shfl(dist, (q - base) * L, 64);
+          }
       }
       take(cs[0], sx, sy, 0, 0);
       cmin = ds[0];
@@ -691,7 +656,7 @@ __device__ __forceinline__ void tz_wave(const TzArgs& ta, int jid, const fme_job
     const bool best_zero = s.bx == 0 && s.by == 0;   // bBestCandidateZero (4857)
 
     // ---- first search: rings around the start, stop 3 rings after the last new best --------------
-    if (G <= 16 || NW > 1) {   // ring by ring: one candidate list per ring, later rings skipped after the stop
+    if (G <= 16) {   // ring by ring: one candidate list per ring, later rings skipped after the stop
       s.ox = s.bx; s.oy = s.by;
       for (int r = 0; r < nr; r++) {
         const int r0 = ring_start(r, c0);
@@ -870,7 +835,7 @@ __device__ __forceinline__ void tz_wave(const TzArgs& ta, int jid, const fme_job
       take((uint32_t)(best >> 32), x, y, 0, 0);
     }
   }
-  if ((NW == 1 ? lane : (int)threadIdx.x) == 0) {   // one writer per PU (NW = 1: per wave)
+  if (lane == 0) {   // one writer per PU
     fme_job* out = ta.jobs_out + jid;
     // ring mode: rcMv after the ring (Backups/4:4881-4882); otherwise the TZ best before the square
     const int bx = ring ? s.bx : tx, by = ring ? s.by : ty;
@@ -894,41 +859,8 @@ __constant__ int kTzW[kNumClasses] = {4, 8, 8, 4, 16, 8, 16, 12, 16, 16, 8, 32, 
 __constant__ int kTzH[kNumClasses] = {8, 4, 8, 16, 4, 16, 8, 16, 12, 16, 32, 8, 32, 16, 32, 24, 32, 64, 16, 64, 32, 64, 48, 64};
 
 
-// Wave-uniform bulk search: one wave per PU of the kernel's unit shape, PUs in class order (CTU
-// order inside a class); blocks dealt to the XCDs in contiguous ranges so each L2 sees one band.
-#ifndef FME_TZW_WAVES   // waves per SIMD (1080p frame, tools/tz_probe.py: 4 -> 6.17 ms, 5 -> 5.84 ms)
-#define FME_TZW_WAVES 5
-#endif
-// Work order: block b runs on XCD b % 8 (round-robin dispatch), and XCD x owns the x-th eighth of
-// every class of this kernel (a spatial band per L2), largest PU class first: the long searches
-// (a 64x64 PU's raster is hundreds of dependent candidate chunks) start at once instead of
-// forming the kernel's tail behind the small ones.
+// Unit-shape kernel of a class: 0 the 4x8 units, 1 the 8x4 units, 2 the 8x8 units.
 __device__ __forceinline__ int tz_kid_of(int c) { return (kTzW[c] % 8) ? 0 : ((kTzH[c] % 8) ? 1 : 2); }
-// XCD x's PU list: for each class of kernel kid, largest first, the x-th eighth of the class.
-// Entry t of the list -> (class, position in class order), or q = -1 past its end.
-__device__ __forceinline__ int tz_entry(const TzSchedule& sc, int kid, int x, int t, int& c) {
-  for (c = kNumClasses - 1; c >= 0; c--) {
-    if (tz_kid_of(c) != kid) continue;
-    const int cnt = sc.class_cnt[c];
-    const int lo = (int)(((long long)cnt * x) >> 3), hi = (int)(((long long)cnt * (x + 1)) >> 3);
-    if (t < hi - lo) return sc.class_off[c] + lo + t;
-    t -= hi - lo;
-  }
-  return -1;
-}
-
-template <int UW, int UH, int KB, int BD = 8>
-__global__ __launch_bounds__(kTzNT) __attribute__((amdgpu_waves_per_eu(FME_TZW_WAVES)))
-void k_tz_wave(TzArgs ta, TzSchedule sc, int kid) {
-  const int x = (int)blockIdx.x & 7;
-  const int t = ((int)blockIdx.x >> 3) * (kTzNT / 64) + (int)(threadIdx.x >> 6);
-  int c;
-  const int q = tz_entry(sc, kid, x, t, c);
-  if (q < 0) return;
-  const int jid = ta.perm[q];
-  const fme_job j = ta.a.jobs[jid];
-  tz_wave<UW, UH, 1, KB, BD>(ta, jid, j, kTzW[c], kTzH[c], tz_ext_at(ta, jid).pred2n_x, tz_ext_at(ta, jid).pred2n_y);
-}
 
 // ---- staged bulk search: PUs grouped by (kernel, reference picture, CTU), a group's search area
 // in LDS (TileRef).  k_tz_pair_count / k_tz_pair_scan / k_tz_pair_scatter build the groups on the
@@ -1027,8 +959,8 @@ __global__ __launch_bounds__(256) void k_tz_pair_scatter(TzArgs ta, TzPairs tp, 
 #ifndef FME_TZS_NT   // threads per workgroup of the staged search (1080p frame, tools/tz_probe.py: 6 waves
 #define FME_TZS_NT 512   // 5.69 ms, 8 waves 4.83 ms; two 45.7 KB tiles per CU at 5 waves/SIMD of registers)
 #endif
-#ifndef FME_TZS_WAVES   // waves per SIMD the staged kernel's registers are sized for
-#define FME_TZS_WAVES FME_TZW_WAVES
+#ifndef FME_TZS_WAVES   // waves per SIMD the staged kernel's registers are sized for (1080p frame,
+#define FME_TZS_WAVES 5   // tools/tz_probe.py: 4 -> 6.17 ms, 5 -> 5.84 ms)
 #endif
 // One launch per unit-shape kernel, one workgroup per group (the grid an upper bound): stage the
 // group's tile, then search its PUs, one wave per PU.  (The three kernels' searches in one launch,
@@ -1084,7 +1016,7 @@ void k_tz_staged(TzArgs ta, TzPairs tp, int kid) {
   for (int p = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6); p < cnt; p += FME_TZS_NT / 64) {
     const int jid = tp.perm[start + p];
     const fme_job j = ta.a.jobs[jid];
-    tz_wave<UW, UH, 1, KB, BD>(ta, jid, j, j.w, j.h, tz_ext_at(ta, jid).pred2n_x, tz_ext_at(ta, jid).pred2n_y, tr);
+    tz_wave<UW, UH, KB, BD>(ta, jid, j, j.w, j.h, tz_ext_at(ta, jid).pred2n_x, tz_ext_at(ta, jid).pred2n_y, tr);
   }
 }
 
@@ -1093,11 +1025,9 @@ void k_tz_staged(TzArgs ta, TzPairs tp, int kid) {
 // post-EMI MVs of earlier levels from global memory (kernel boundaries order them) and no level
 // waits for the host.  ch.psrc[q] >= 0: job q's m_integerMv2Nx2N is job psrc[q]'s result; -1: its
 // ext already holds it.
-#ifndef FME_TZL_WAVES
-#define FME_TZL_WAVES 1   // waves per chain job (A/B: 8 waves 276 ms per P frame, spilling; 1 wave 198 ms)
-#endif
+// One wave per chain job (A/B: 8 waves 276 ms per P frame, spilling; 1 wave 198 ms).
 template <int BD>
-__global__ __launch_bounds__(64 * FME_TZL_WAVES) void k_tz_level(TzArgs ta, TzChain ch, int first) {
+__global__ __launch_bounds__(64) void k_tz_level(TzArgs ta, TzChain ch, int first) {
   const int q = first + (int)blockIdx.x;
   const int PW = ta.a.jobs[q].w, PH = ta.a.jobs[q].h;   // shapes checked by the host
   const int ps = ch.psrc[q];
@@ -1109,9 +1039,9 @@ __global__ __launch_bounds__(64 * FME_TZL_WAVES) void k_tz_level(TzArgs ta, TzCh
   }
   const int kid = (PW % 8) ? 0 : ((PH % 8) ? 1 : 2);
   const fme_job j = ta.a.jobs[q];
-  if (kid == 0) tz_wave<4, 8, FME_TZL_WAVES, -1, BD>(ta, q, j, PW, PH, px, py);
-  else if (kid == 1) tz_wave<8, 4, FME_TZL_WAVES, -1, BD>(ta, q, j, PW, PH, px, py);
-  else tz_wave<8, 8, FME_TZL_WAVES, -1, BD>(ta, q, j, PW, PH, px, py);
+  if (kid == 0) tz_wave<4, 8, -1, BD>(ta, q, j, PW, PH, px, py);
+  else if (kid == 1) tz_wave<8, 4, -1, BD>(ta, q, j, PW, PH, px, py);
+  else tz_wave<8, 8, -1, BD>(ta, q, j, PW, PH, px, py);
 }
 
 }  // namespace
@@ -1131,25 +1061,10 @@ hipError_t launch_tz_levels(const TzArgs& ta, const TzChain& ch, const int32_t* 
   for (int lv = 0; lv < ch.nlev; lv++) {
     const int n = h_lvl_off[lv + 1] - h_lvl_off[lv];
     if (n <= 0) continue;
-    if (bit_depth > 8) hipLaunchKernelGGL(k_tz_level<10>, dim3(n), dim3(64 * FME_TZL_WAVES), 0, s, ta, ch, h_lvl_off[lv]);
-    else hipLaunchKernelGGL(k_tz_level<8>, dim3(n), dim3(64 * FME_TZL_WAVES), 0, s, ta, ch, h_lvl_off[lv]);
+    if (bit_depth > 8) hipLaunchKernelGGL(k_tz_level<10>, dim3(n), dim3(64), 0, s, ta, ch, h_lvl_off[lv]);
+    else hipLaunchKernelGGL(k_tz_level<8>, dim3(n), dim3(64), 0, s, ta, ch, h_lvl_off[lv]);
   }
   return hipGetLastError();
-}
-
-// Unit shape of a class for the integer search: 8 wide / tall where the PU allows, else 4.
-int tz_kernel_of(int cls) {
-  const int w = kClassW[cls], h = kClassH[cls];
-  const int uw = (w % 8) == 0 ? 8 : 4, uh = (h % 8) == 0 ? 8 : 4;
-  return uw == 4 ? 0 : (uh == 4 ? 1 : 2);
-}
-int tz_lanes_per_pu(int cls) {
-  const int w = kClassW[cls], h = kClassH[cls];
-  const int uw = (w % 8) == 0 ? 8 : 4, uh = (h % 8) == 0 ? 8 : 4;
-  const int lr = (w / uw) * (h / uh);
-  int l = 1;
-  while (l < lr) l <<= 1;
-  return l;
 }
 
 hipError_t launch_tz_pairs(const TzArgs& ta, const TzPairs& tp, const uint8_t* cls, int n, hipStream_t s) {
@@ -1177,34 +1092,5 @@ hipError_t launch_tz_staged(const TzArgs& ta, const TzPairs& tp, int kid, bool k
   }
   return hipGetLastError();
 }
-
-// Wave-uniform bulk search of kernel kid: sc.prefix in waves (one per PU).
-hipError_t launch_tz_wave(const TzArgs& ta, const TzSchedule& sc, int kid, bool keyed, int bit_depth, hipStream_t s) {
-  int share = 0;   // the largest per-XCD share of this kernel's PUs (waves)
-  for (int x = 0; x < 8; x++) {
-    int n = 0;
-    for (int c = 0; c < kNumClasses; c++)
-      if (tz_kernel_of(c) == kid)
-        n += (int)(((long long)sc.class_cnt[c] * (x + 1)) >> 3) - (int)(((long long)sc.class_cnt[c] * x) >> 3);
-    share = std::max(share, n);
-  }
-  if (share <= 0) return hipSuccess;
-  const int blocks = 8 * ((share + kTzNT / 64 - 1) / (kTzNT / 64));
-  if (bit_depth > 8) {   // one form: the 10-bit key rows are sample pairs either way
-    if (kid == 0) hipLaunchKernelGGL((k_tz_wave<4, 8, -1, 10>), dim3(blocks), dim3(kTzNT), 0, s, ta, sc, 0);
-    else if (kid == 1) hipLaunchKernelGGL((k_tz_wave<8, 4, -1, 10>), dim3(blocks), dim3(kTzNT), 0, s, ta, sc, 1);
-    else hipLaunchKernelGGL((k_tz_wave<8, 8, -1, 10>), dim3(blocks), dim3(kTzNT), 0, s, ta, sc, 2);
-  } else if (keyed) {
-    if (kid == 0) hipLaunchKernelGGL((k_tz_wave<4, 8, -1>), dim3(blocks), dim3(kTzNT), 0, s, ta, sc, 0);
-    else if (kid == 1) hipLaunchKernelGGL((k_tz_wave<8, 4, -1>), dim3(blocks), dim3(kTzNT), 0, s, ta, sc, 1);
-    else hipLaunchKernelGGL((k_tz_wave<8, 8, -1>), dim3(blocks), dim3(kTzNT), 0, s, ta, sc, 2);
-  } else {
-    if (kid == 0) hipLaunchKernelGGL((k_tz_wave<4, 8, 0>), dim3(blocks), dim3(kTzNT), 0, s, ta, sc, 0);
-    else if (kid == 1) hipLaunchKernelGGL((k_tz_wave<8, 4, 0>), dim3(blocks), dim3(kTzNT), 0, s, ta, sc, 1);
-    else hipLaunchKernelGGL((k_tz_wave<8, 8, 0>), dim3(blocks), dim3(kTzNT), 0, s, ta, sc, 2);
-  }
-  return hipGetLastError();
-}
-
 
 }  // namespace fme

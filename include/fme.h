@@ -425,7 +425,12 @@ int fme_refine_status(fme_ctx* ctx);
  *   bi-pred jobs: xPatternSearch (TEncSearch.cpp:4627-4680), every point of lt..rb in raster order.
  * The metric is the modified integer-ME one of the batch path (SSE, SAD12/24/48 with FEN row
  * subsampling) plus the MV cost at cost scale 2.  On return job.mv_x/mv_y hold the integer MV
- * (ready for fme_refine) and sad[i] = ruiSAD (distortion at that MV).                             */
+ * (ready for fme_refine) and sad[i] = ruiSAD (distortion at that MV).
+ * Limit: the search groups its PUs by (picture slot, CTU), and (highest bound picture id + 1) x
+ * (CTU columns x CTU rows of the largest bound picture, 64x64 CTUs) may be at most 2^20 = 1,048,576
+ * (sixty-four 8K pictures make 64 x 120 x 68 = 522,240); beyond that every fme_integer_search*
+ * entry point, and a producer through its searches, returns FME_E_UNSUPPORTED with nothing
+ * enqueued.                                                                                      */
 #define FME_TZ_PRED2NX2N 0x01u
 #define FME_TZ_RING      0x02u   /* the backups' xTZSearch tail: square (distance 1) + ring (distance 2),
                                     every distortion pushed (fme_integer_search_ring; see

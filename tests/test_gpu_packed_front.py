@@ -1,7 +1,7 @@
 """The batch front end on packed jobs read in place: fme_refine*_packed_device hand the caller's
-16-byte rows to every kernel of the batch (k_classify computes the keyed jobs' offsets, k_scatter
-builds the schedule and zeroes the next batch's counters), with no unpacked copy and no fill
-dispatch between batches.
+16-byte rows to every kernel of the batch (k_front computes the keyed jobs' offsets and groups the
+jobs by class; its last workgroup builds the schedule and zeroes the counters of the batch after
+next), with no unpacked copy and no fill dispatch between batches.
 
 Everything is checked against the unpacked entry points on fme_unpack_jobs(fme_pack_jobs(jobs)),
 field for field, and against the CPU oracle on those jobs, on a 416x240 picture."""

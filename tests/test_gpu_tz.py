@@ -115,6 +115,30 @@ def test_tz_device_and_timing():
     assert TZ_EXT_DTYPE.itemsize == 12
 
 
+def test_tz_too_many_picture_ctu_pairs_refused():
+    """The search groups its PUs by (picture slot, CTU): (highest bound id + 1) x CTUs of the largest
+    bound picture may be at most 2^20.  An 8256 x 8192 plane (129 x 128 CTUs) at id 63 makes
+    64 * 129 * 128 = 1,056,768: the call is refused with FME_E_UNSUPPORTED before anything is planned
+    or enqueued, so the same context then gives the golden's MVs and SADs."""
+    import torch
+    from nnfme.abi import E_UNSUPPORTED
+    from nnfme.runtime import FmeError
+    g = load_golden("tz_far_fen0_sr32")
+    ctx = _ctx(g)
+    dev = torch.device("cuda", 0)
+    big = torch.zeros((8192, 8256), dtype=torch.uint8, device=dev)
+    ctx.bind_picture_device(63, big.data_ptr(), 8256, 8256, 8192)
+    with pytest.raises(FmeError) as err:
+        ctx.integer_search(g["jobs"][:1], g["ext"][:1])
+    assert err.value.code == E_UNSUPPORTED
+    assert "1056768" in str(err.value) and "1048576" in str(err.value)
+    small = torch.zeros((64, 64), dtype=torch.uint8, device=dev)
+    ctx.bind_picture_device(63, small.data_ptr(), 64, 64, 64)
+    jobs, sad = ctx.integer_search(g["jobs"], g["ext"])
+    assert np.array_equal(jobs["mv_x"], g["mv_x"]) and np.array_equal(jobs["mv_y"], g["mv_y"])
+    assert np.array_equal(sad, g["sad"])
+
+
 @pytest.mark.parametrize("case", ["tz_enhanced_fen1", "tz_full_sr8_fen1", "tz10_enhanced_fen1", "tz10_full_sr8_fen3"])
 def test_tz2_device_and_mode_flags(case):
     """FastSearch 0 / 3 (fme_tz_ext2) through the device entry point; the same jobs through the
