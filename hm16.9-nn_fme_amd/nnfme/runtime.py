@@ -155,6 +155,19 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data)
 
 
+def _rows(a, dtype):
+    """A 2-D sample plane as (array, row stride in samples) for the calls that take a stride: a view
+    whose rows are contiguous but further apart than their width (a slice of a wider array) is
+    passed as it is, anything else (another dtype, a column step, reversed rows) is copied first."""
+    a = np.asarray(a)
+    item = np.dtype(dtype).itemsize
+    if (a.ndim == 2 and a.dtype == dtype and a.shape[1] > 0 and a.strides[1] == item
+            and a.strides[0] % item == 0 and a.strides[0] >= a.shape[1] * item):
+        return a, a.strides[0] // item
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a, a.shape[1]
+
+
 class FmeContext:
     """One device context: pictures, lambdas, keys, NN weights and the carried NN state."""
 
@@ -194,9 +207,11 @@ class FmeContext:
 
     # -- state --------------------------------------------------------------------------
     def set_picture(self, pid, luma, stream=None):
-        luma = np.ascontiguousarray(luma, dtype=np.uint16 if self.bit_depth > 8 else np.uint8)
+        """A host plane (uint8, or uint16 at bit depth 10); a row-strided view (a slice of a wider
+        array) is uploaded from where it lies, with its own stride."""
+        luma, stride = _rows(luma, np.uint16 if self.bit_depth > 8 else np.uint8)
         h, w = luma.shape
-        _check(self.lib, self.lib.fme_set_picture(self.h, pid, _ptr(luma), w, w, h, stream))
+        _check(self.lib, self.lib.fme_set_picture(self.h, pid, _ptr(luma), stride, w, h, stream))
 
     def bind_picture_device(self, pid, data_ptr, stride, width, height):
         """A caller-owned device plane (8-bit samples, or uint16 at bit depth 10; stride in samples)."""
@@ -205,10 +220,12 @@ class FmeContext:
     def set_picture_chroma(self, pid, cb, cr, stream=None):
         """4:2:0 chroma planes of picture pid: uint8, or uint16 samples in a bit-depth-10 context."""
         dt = np.uint16 if self.bit_depth > 8 else np.uint8
-        cb = np.ascontiguousarray(cb, dtype=dt)
-        cr = np.ascontiguousarray(cr, dtype=dt)
+        (cb, sb), (cr, sr) = _rows(cb, dt), _rows(cr, dt)
+        if sb != sr:   # the call takes one stride for both planes
+            cb, cr = np.ascontiguousarray(cb), np.ascontiguousarray(cr)
+            sb = cb.shape[1]
         assert cb.shape == cr.shape
-        _check(self.lib, self.lib.fme_set_picture_chroma(self.h, pid, _ptr(cb), _ptr(cr), cb.shape[1], stream))
+        _check(self.lib, self.lib.fme_set_picture_chroma(self.h, pid, _ptr(cb), _ptr(cr), sb, stream))
 
     def set_picture_yuv(self, pid, y, cb, cr, stream=None):
         self.set_picture(pid, y, stream)

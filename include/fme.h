@@ -182,14 +182,26 @@ int         fme_destroy(fme_ctx* ctx);
 const char* fme_last_error(void);
 
 /* ---- pictures ----------------------------------------------------------------------- *
- * 8-bit luma planes, unpadded (width x height, row stride in bytes; at bit_depth 10 `luma`
- * points to uint16_t samples and the stride counts samples).  The path reads
+ * 8-bit luma planes: `luma` points at sample (0, 0) of width x height samples, rows `stride`
+ * (>= width) bytes apart; at bit_depth 10 `luma` points to uint16_t samples and the stride counts
+ * samples.  No border is needed, and none around the plane is read: the path reads
  * outside the picture with edge replication, which equals HM's padded TComPicYuv
  * (extendPicBorder, TComPicYuv.cpp:229-276) for every MV TComDataCU::clipMv admits.  */
 int fme_set_picture(fme_ctx* ctx, int id, const uint8_t* luma, int stride, int width, int height,
                     void* stream);
 /* Zero-copy: bind a device-resident plane owned by the caller (e.g. a buffer filled by an
- * RCCL broadcast).  It must stay valid while jobs that use `id` run. */
+ * RCCL broadcast, or an encoder's padded picture).  It must stay valid while jobs that use `id`
+ * run.  Layout contract (tests/test_gpu_bound_planes.py):
+ *   - `d_luma` points at sample (0, 0) of the picture, which may lie anywhere inside a larger
+ *     allocation (HM's TComPicYuv: `margin` rows and columns in, stride = width + 2 * margin);
+ *   - `stride` is any value >= width, in samples (bytes at bit depth 8, uint16 at 10);
+ *   - `d_luma` need only be aligned to the sample size (1 byte, or 2 at bit depth 10);
+ *   - when `d_luma` and the row pitch in bytes are multiples of 4 (4 * k samples at bit depth 8),
+ *     the prediction kernels (motion compensation, prediction error, skip check, cost surface,
+ *     producers) take their dword-load paths, otherwise their per-sample paths; the refinement and
+ *     the integer search load at any alignment.  The results do not depend on the layout;
+ *   - only the width x height samples are ever read: positions outside the picture are
+ *     edge-replicated from inside it, whatever surrounds the plane in memory. */
 int fme_bind_picture_device(fme_ctx* ctx, int id, const uint8_t* d_luma, int stride, int width,
                             int height);
 
@@ -198,6 +210,11 @@ int fme_bind_picture_device(fme_ctx* ctx, int id, const uint8_t* d_luma, int str
  * motion compensation reads chroma.                                                         */
 int fme_set_picture_chroma(fme_ctx* ctx, int id, const uint8_t* cb, const uint8_t* cr, int stride,
                            void* stream);
+/* Zero-copy chroma, under fme_bind_picture_device's layout contract at chroma size: `d_cb` and
+ * `d_cr` point at sample (0, 0) of two (width/2) x (height/2) planes that share `stride`, any
+ * value >= width/2 in samples; a base aligned to the sample size; bases and a row pitch that are
+ * multiples of 4 bytes select the dword-load path (independently of the luma plane's), any other
+ * layout the per-sample path; nothing outside the planes is read. */
 int fme_bind_picture_chroma_device(fme_ctx* ctx, int id, const uint8_t* d_cb, const uint8_t* d_cr,
                                    int stride);
 

@@ -213,6 +213,25 @@ def test_mc_unaligned_output_planes():
         assert (p[:, w:] == _SENTINEL).all()
 
 
+def test_mc10_unaligned_output_planes():
+    """Bit depth 10, device form, int16 output planes with odd strides W + 1 (luma) and W/2 + 1
+    (chroma): every other row starts 2 bytes off a dword, where k_mc<true>'s store_row writes one
+    16-bit sample at a time.  The W x H views equal the oracle's contiguous planes and the padding
+    column keeps the sentinel."""
+    import torch
+    from nnfme.runtime import FmeContext
+    W, H, pics, jobs, expect = _small(10)
+    ctx = FmeContext(nn_mode=0, bit_depth=10)
+    for k, p in pics.items():
+        ctx.set_picture_yuv(k, *p)
+    got = tuple(p.view(np.uint16) for p in _mc_device(ctx, jobs, W, H, W + 1, W // 2 + 1, torch.int16))
+    assert ctx.mc_invalid_count() == 0
+    exp = expect(len(jobs))
+    _same((got[0][:, :W], got[1][:, :W // 2], got[2][:, :W // 2]), exp, "unaligned 10-bit planes")
+    for p, w in zip(got, (W, W // 2, W // 2)):
+        assert (p[:, w:] == _SENTINEL).all()
+
+
 def test_mc_invalid_jobs():
     from nnfme.runtime import FmeError
     W, H = 128, 64

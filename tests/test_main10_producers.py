@@ -9,6 +9,7 @@ TComYuv::removeHighFreq at bitDepth 10; its integer search against the tz10_* go
 (tests/test_oracle.py); its sub-pel path against the main10_* goldens.  The producer loops then run
 on the GPU against the oracle's (the composition is restated, as at 8 bits: test_pred_inter.py).
 Integer outputs: bit-exact."""
+import functools
 import os
 
 import numpy as np
@@ -23,9 +24,13 @@ def _pics10(n=5):
     return {i: synth.synth_luma_hbd(W, H, t, bit_depth=10) for i, t in zip(range(n), (7, 6, 5, 4, 0, 3))}
 
 
-def _setup(eng, pics):
-    for k, v in pics.items():
-        eng.set_picture(k, v)
+def _setup(eng, pics, bind=None):
+    """bind(eng, pics): how the pictures reach the engine (default: set_picture of each)."""
+    if bind is not None:
+        bind(eng, pics)
+    else:
+        for k, v in pics.items():
+            eng.set_picture(k, v)
     for lid, lam in enumerate(synth.LDP_LAMBDA[22]):
         eng.set_lambda(lid, lam)
 
@@ -158,26 +163,31 @@ def test_main10_pred_inter_p_matches_oracle():
     assert len(np.unique(got["ref_idx"])) > 1
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("fen", [1, 0])
-def test_main10_pred_inter_b_matches_oracle(fen):
-    """A 10-bit B request stream (2 + 2 references, one shared; FEN 1: one bi-pred iteration, FEN 0:
-    four) on the GPU against the oracle: the bi-pred keys (k_bi_key<true>), their integer searches and
-    refinements, the uni / bi decision."""
+@functools.lru_cache(maxsize=None)
+def main10_pred_inter_b_case(fen):
+    """(pictures, requests, the oracle's results, its final NN state), computed once per FEN and
+    shared (read only)."""
     from nnfme import weights
-    from nnfme.runtime import FmeContext
     from oracle import Oracle
     pics = _pics10(6)
     rng = np.random.default_rng(65 + fen)
     reqs = synth.make_pu_requests_b(rng, W, H, org_id=4, l0=[(0, 1), (1, 2)], l1=[(5, -1), (1, 2)], lambda_id=0,
                                     max_depth=3, lossless_frac=0.05)
-    ctx = FmeContext(nn_mode=1, qp=22, fast_inter_mode=fen, bit_depth=10)
     orc = Oracle(nn_mode=1, qp=22, fast_inter_mode=fen, bit_depth=10)
     orc.load_nn(weights.load_weights(22))
-    _setup(ctx, pics)
     _setup(orc, pics)
-    got = ctx.pred_inter_b(reqs)
     exp = orc.pred_inter_b(reqs)
+    return pics, reqs, exp, orc.nn_get_state()
+
+
+def check_main10_pred_inter_b_matches_oracle(fen, bind=None):
+    """The body of test_main10_pred_inter_b_matches_oracle; bind(ctx, pics) gives the GPU context
+    its pictures (tests/test_gpu_bound_planes.py binds padded device planes)."""
+    from nnfme.runtime import FmeContext
+    pics, reqs, exp, state = main10_pred_inter_b_case(fen)
+    ctx = FmeContext(nn_mode=1, qp=22, fast_inter_mode=fen, bit_depth=10)
+    _setup(ctx, pics, bind)
+    got = ctx.pred_inter_b(reqs)
     for f in abi.PU_RES_B_DTYPE.names:
         if f == "reserved":
             continue
@@ -185,5 +195,14 @@ def test_main10_pred_inter_b_matches_oracle(fen):
         if bad.ndim > 1:
             bad = bad.reshape(len(bad), -1).any(axis=1)
         assert not bad.any(), f"{f}: {int(bad.sum())} of {len(bad)} requests differ (first {int(np.flatnonzero(bad)[0])})"
-    assert np.array_equal(ctx.nn_get_state(), orc.nn_get_state())
+    assert np.array_equal(ctx.nn_get_state(), state)
     assert set(np.unique(got["inter_dir"])) == {1, 2, 3}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fen", [1, 0])
+def test_main10_pred_inter_b_matches_oracle(fen):
+    """A 10-bit B request stream (2 + 2 references, one shared; FEN 1: one bi-pred iteration, FEN 0:
+    four) on the GPU against the oracle: the bi-pred keys (k_bi_key<true>), their integer searches and
+    refinements, the uni / bi decision."""
+    check_main10_pred_inter_b_matches_oracle(fen)

@@ -7,6 +7,7 @@ reference choice (3845-3853).  The composition itself has no reference fixture (
 needs Eigen): its pieces are pinned, the glue is restated twice (C oracle, host
 runtime) and once more here in Python for the AMVP / xCheckBestMVP / reference-choice rules.
 Integer outputs: bit-exact."""
+import functools
 import os
 
 import numpy as np
@@ -22,9 +23,13 @@ def _pics():
     return {i: synth.synth_luma(W, H, t) for i, t in zip(range(5), (7, 6, 5, 4, 0))}
 
 
-def _setup(eng, pics):
-    for k, v in pics.items():
-        eng.set_picture(k, v)
+def _setup(eng, pics, bind=None):
+    """bind(eng, pics): how the pictures reach the engine (default: set_picture of each)."""
+    if bind is not None:
+        bind(eng, pics)
+    else:
+        for k, v in pics.items():
+            eng.set_picture(k, v)
     for lid, lam in enumerate(synth.LDP_LAMBDA[22]):
         eng.set_lambda(lid, lam)
 
@@ -160,33 +165,47 @@ def test_oracle_amvp_choice_and_check_best_mvp():
 
 
 # ---- GPU parity (through the C ABI) ---------------------------------------------------------------
-@pytest.mark.gpu
-def test_pred_inter_matches_oracle():
-    """A CTU-quadtree request stream (64 -> 8 CUs, AMP, 4 references, NN on, 5 % lossless) on the
-    GPU against the oracle, in two calls so that m_integerMv2Nx2N and the NN state cross calls."""
+@functools.lru_cache(maxsize=None)
+def pred_inter_case():
+    """(pictures, requests, the oracle's results, its final NN state), computed once and shared
+    (read only)."""
     from nnfme import weights
-    from nnfme.runtime import FmeContext
     from oracle import Oracle
     pics = _pics()
     rng = np.random.default_rng(21)
     reqs = synth.make_pu_requests(rng, W, H, org_id=4, ref_ids=[0, 1, 2, 3], lambda_id=0, max_depth=3,
                                   lossless_frac=0.05)
-    ctx = FmeContext(nn_mode=1, qp=22, fast_inter_mode=1)
     orc = Oracle(nn_mode=1, qp=22, fast_inter_mode=1)
     orc.load_nn(weights.load_weights(22))
-    _setup(ctx, pics)
     _setup(orc, pics)
+    exp = orc.pred_inter_p(reqs)
+    return pics, reqs, exp, orc.nn_get_state()
+
+
+def check_pred_inter_matches_oracle(bind=None):
+    """The body of test_pred_inter_matches_oracle; bind(ctx, pics) gives the GPU context its
+    pictures (tests/test_gpu_bound_planes.py binds padded device planes)."""
+    from nnfme.runtime import FmeContext
+    pics, reqs, exp, state = pred_inter_case()
+    ctx = FmeContext(nn_mode=1, qp=22, fast_inter_mode=1)
+    _setup(ctx, pics, bind)
     cut = len(reqs) // 3 + 7
     got = np.concatenate([ctx.pred_inter_p(reqs[:cut]), ctx.pred_inter_p(reqs[cut:])])
-    exp = orc.pred_inter_p(reqs)
     for f in ("mv_x", "mv_y", "mvp_x", "mvp_y", "ref_idx", "mvp_idx", "bits", "cost", "ref_cost", "ref_bits",
               "ref_mv", "ref_mvp_idx"):
         bad = got[f] != exp[f]
         if bad.ndim > 1:
             bad = bad.reshape(len(bad), -1).any(axis=1)
         assert not bad.any(), f"{f}: {int(bad.sum())} of {len(bad)} requests differ (first {int(np.flatnonzero(bad)[0])})"
-    assert np.array_equal(ctx.nn_get_state(), orc.nn_get_state())
+    assert np.array_equal(ctx.nn_get_state(), state)
     assert len(np.unique(got["ref_idx"])) > 1
+
+
+@pytest.mark.gpu
+def test_pred_inter_matches_oracle():
+    """A CTU-quadtree request stream (64 -> 8 CUs, AMP, 4 references, NN on, 5 % lossless) on the
+    GPU against the oracle, in two calls so that m_integerMv2Nx2N and the NN state cross calls."""
+    check_pred_inter_matches_oracle()
 
 
 @pytest.mark.gpu

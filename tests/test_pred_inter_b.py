@@ -30,9 +30,13 @@ def _pics():
     return {i: synth.synth_luma(W, H, t) for i, t in zip(range(6), (7, 6, 5, 4, 0, 3))}
 
 
-def _setup(eng, pics):
-    for k, v in pics.items():
-        eng.set_picture(k, v)
+def _setup(eng, pics, bind=None):
+    """bind(eng, pics): how the pictures reach the engine (default: set_picture of each)."""
+    if bind is not None:
+        bind(eng, pics)
+    else:
+        for k, v in pics.items():
+            eng.set_picture(k, v)
     for lid, lam in enumerate(synth.LDP_LAMBDA[22]):
         eng.set_lambda(lid, lam)
 
@@ -342,10 +346,9 @@ def test_pred_inter_b_matches_oracle():
     assert set(np.unique(got["inter_dir"])) == {1, 2, 3}
 
 
-@pytest.mark.gpu
-def test_device_bipred_keys_drive_refine_like_host_keys():
-    """fme_build_bipred_keys (k_bi_key) gives the keys synth.bipred_keys computes: bi-pred refine
-    jobs read them and equal the same jobs on host-uploaded keys (and the oracle)."""
+def check_device_bipred_keys_drive_refine_like_host_keys(bind=None):
+    """The body of test_device_bipred_keys_drive_refine_like_host_keys; bind(ctx, pics) gives the GPU
+    contexts their pictures (tests/test_gpu_bound_planes.py binds padded device planes)."""
     from nnfme.runtime import FmeContext
     from oracle import Oracle
     pics = _pics()
@@ -356,7 +359,7 @@ def test_device_bipred_keys_drive_refine_like_host_keys():
     keys = synth.bipred_keys(reqs, pics, kc)
     dev_ctx, host_ctx = FmeContext(nn_mode=1, qp=22), FmeContext(nn_mode=1, qp=22)
     for c in (dev_ctx, host_ctx):
-        _setup(c, pics)
+        _setup(c, pics, bind)
     dev_ctx.build_bipred_keys(reqs, kc)
     host_ctx.set_keys(keys)
     a, b = dev_ctx.refine(jobs), host_ctx.refine(jobs)
@@ -374,6 +377,13 @@ def test_device_bipred_keys_drive_refine_like_host_keys():
     from nnfme.runtime import FmeError
     with pytest.raises(FmeError):
         dev_ctx.build_bipred_keys(bad, kc)
+
+
+@pytest.mark.gpu
+def test_device_bipred_keys_drive_refine_like_host_keys():
+    """fme_build_bipred_keys (k_bi_key) gives the keys synth.bipred_keys computes: bi-pred refine
+    jobs read them and equal the same jobs on host-uploaded keys (and the oracle)."""
+    check_device_bipred_keys_drive_refine_like_host_keys()
 
 
 @pytest.mark.gpu
