@@ -77,6 +77,133 @@ def synth_luma_hbd(width, height, t, bit_depth=10, seed=None):
     return np.clip(np.rint(acc * scale), 0, (1 << bit_depth) - 1).astype(np.uint16)
 
 
+# ---- stress content: saturated, flat and two-level pictures, keys at the ends of their range -------
+STRESS_KINDS = ("checker1", "vstripe2", "hstripe2", "checker4", "binary", "uniform", "zero", "full", "flat",
+                "twolevel", "blocks8")
+STRESS_SEEDED = ("binary", "uniform", "twolevel")   # the kinds that draw from a generator
+KEY_PATTERNS = ("sample", "block4", "pair", "high", "low")
+
+
+def stress_picture(width, height, bit_depth, kind, index=0, seed=5):
+    """One plane (uint8, or uint16 above 8 bits) of the content the sinusoids never produce; with
+    hi = 2^bit_depth - 1 and mid = 2^(bit_depth - 1):
+
+      checker1  ((x + y + index) & 1) * hi     both filters at their extreme outputs, |d| = hi
+      vstripe2  ((x >> 1) & 1) * hi            the horizontal filter at its extremes alone
+      hstripe2  ((y >> 1) & 1) * hi            the vertical one alone
+      checker4  a 4x4 checker of 0 / hi        edges on the 4x4 transform's grid (index shifts it)
+      binary    seeded random {0, hi}          the largest sums: SADs, SSEs, Hadamard rows
+      uniform   seeded random over 0..hi       every sample value, every byte of the packed forms
+      zero / full / flat                       constant 0 / hi / mid: every candidate ties
+      twolevel  mid + seeded {0, 1}            ties among distortions that are not all equal
+      blocks8   mid + 40 * ((((x + 3 * index) >> 3) + (y >> 3)) & 1)   moving edges, ties inside blocks
+
+    index is the picture's place in a sequence (a reference slot, a POC): the seeded kinds draw
+    another plane for each."""
+    hi, mid = (1 << bit_depth) - 1, 1 << (bit_depth - 1)
+    dt = np.uint16 if bit_depth > 8 else np.uint8
+    y, x = np.mgrid[0:height, 0:width]
+    if kind in STRESS_SEEDED:
+        rng = np.random.default_rng([seed, index, bit_depth, STRESS_SEEDED.index(kind)])
+        if kind == "binary":
+            p = rng.integers(0, 2, (height, width)) * hi
+        elif kind == "uniform":
+            p = rng.integers(0, hi + 1, (height, width))
+        else:
+            p = mid + rng.integers(0, 2, (height, width))
+    elif kind == "checker1":
+        p = ((x + y + index) & 1) * hi
+    elif kind == "vstripe2":
+        p = ((x >> 1) & 1) * hi
+    elif kind == "hstripe2":
+        p = ((y >> 1) & 1) * hi
+    elif kind == "checker4":
+        p = (((x >> 2) + (y >> 2) + index) & 1) * hi
+    elif kind in ("zero", "full", "flat"):
+        p = np.full((height, width), {"zero": 0, "full": hi, "flat": mid}[kind])
+    elif kind == "blocks8":
+        p = mid + 40 * ((((x + 3 * index) >> 3) + (y >> 3)) & 1)
+    else:
+        raise ValueError(f"unknown stress kind {kind!r}")
+    return p.astype(dt)
+
+
+def stress_pictures(width, height, bit_depth, name, slots=5, seed=5):
+    """{slot: plane} of one stress set.  name: a kind (slot k = stress_picture(..., index=k)), or
+    "ORG-REF": the last slot (the original's) of kind ORG, every other slot of kind REF."""
+    org, _, ref = name.partition("-")
+    kinds = [ref or org] * (slots - 1) + [org]
+    return {k: stress_picture(width, height, bit_depth, kinds[k], index=k, seed=seed) for k in range(slots)}
+
+
+def extreme_keys(rng, jobs, keys, bit_depth, pattern, frac=1.0):
+    """Overwrites, in keys, the key blocks of a share frac of the bi-pred jobs (key_offset >= 0) with
+    the two ends of the range of 2 * org - pred_other, -hi and 2 * hi: per "sample" (drawn from rng),
+    in 4x4 blocks ("block4"), in 2x1 blocks ("pair", finer than either transform), all 2 * hi
+    ("high") or all -hi ("low"); a tuple of patterns is dealt out over the chosen jobs in turn.
+    Returns the indices of the jobs it changed."""
+    hi = (1 << bit_depth) - 1
+    sel = np.flatnonzero(((jobs["flags"] & JOB_BIPRED) != 0) & (jobs["key_offset"] >= 0))
+    sel = sel[rng.random(len(sel)) < frac]
+    patterns = (pattern,) if isinstance(pattern, str) else tuple(pattern)
+    for k, i in enumerate(sel):
+        pattern = patterns[k % len(patterns)]
+        w, h, off = int(jobs["w"][i]), int(jobs["h"][i]), int(jobs["key_offset"][i])
+        yy, xx = np.mgrid[0:h, 0:w]
+        if pattern == "sample":
+            top = rng.integers(0, 2, (h, w))
+        elif pattern == "block4":
+            top = ((yy >> 2) + (xx >> 2)) & 1
+        elif pattern == "pair":
+            top = ((xx >> 1) + yy) & 1
+        elif pattern in ("high", "low"):
+            top = np.full((h, w), int(pattern == "high"))
+        else:
+            raise ValueError(f"unknown key pattern {pattern!r}")
+        keys[off:off + w * h] = np.where(top == 1, 2 * hi, -hi).astype(np.int16).reshape(-1)
+    return sel
+
+
+def stress_refine_batch(rng, width, height, bit_depth, pictures):
+    """96 refinement jobs on a stress set: the 24 PU shapes four times over.  Round 0: uni-pred with
+    the EMI step; round 1: bi-pred, every key block at the ends of the key range, the five
+    KEY_PATTERNS dealt out over the shapes; round 2: every third shape bi-pred on the key of a
+    displaced block of another picture, the others uni-pred; round 3: every fourth shape lossless.
+    Returns (jobs, keys)."""
+    shapes = np.array(ALL_PU_SIZES)
+    w, h = np.tile(shapes[:, 0], 4), np.tile(shapes[:, 1], 4)
+    n = len(w)
+    jobs = make_jobs(rng, width, height, n, 4, [0, 1, 2, 3], [0, 1, 2, 3], sizes=(w, h))
+    i = np.arange(n)
+    bi = (i // 24 == 1) | ((i // 24 == 2) & (i % 3 == 0))
+    jobs["flags"][bi] = JOB_BIPRED
+    jobs["key_offset"][bi] = -2
+    jobs["flags"][(i // 24 == 3) & (i % 4 == 0)] |= 0x04   # FME_JOB_LOSSLESS
+    keys = make_bipred_keys(rng, jobs, pictures)
+    extreme = jobs[:48].copy()   # rounds 0 and 1: the keyed jobs among them are round 1
+    extreme_keys(rng, extreme, keys, bit_depth, KEY_PATTERNS)
+    return jobs, keys
+
+
+def stress_tz_batch(rng, width, height, bit_depth, pictures, calls_per_ctu=30, search_range=8):
+    """Integer-search jobs on a stress set: every PU shape equally often (the 64x64 sums are the ones
+    near the 32-bit ceiling), lambda slots 0..4 (the caller binds 0.0 to slot 4), 30 % bi-pred, half
+    of those on keys at the ends of the key range.  Returns (jobs, ext, keys)."""
+    mix = [(s, 1.0) for s in ALL_PU_SIZES]
+    jobs, ext = make_tz_jobs(rng, width, height, calls_per_ctu, 4, [0, 1, 2, 3], [0, 1, 2, 3, 4], mix=mix,
+                             bipred_frac=0.3, search_range=search_range)
+    keys = make_bipred_keys(rng, jobs, pictures)
+    extreme_keys(rng, jobs, keys, bit_depth, KEY_PATTERNS, frac=0.5)
+    return jobs, ext, keys
+
+
+def stress_yuv(width, height, bit_depth, kind, slots=3, seed=5):
+    """{slot: (Y, Cb, Cr)} 4:2:0 reference pictures of one stress kind (each plane its own index)."""
+    return {k: (stress_picture(width, height, bit_depth, kind, k, seed),
+                stress_picture(width // 2, height // 2, bit_depth, kind, k + 10, seed),
+                stress_picture(width // 2, height // 2, bit_depth, kind, k + 20, seed)) for k in range(slots)}
+
+
 def _clip_mv_qpel(v, pos, pic, size_max=MAX_CU):
     """TComDataCU::clipMv on quarter-pel values, with the PU position standing in for the
     CU position (TComDataCU.cpp:2778-2785)."""

@@ -78,6 +78,11 @@ typedef struct fme_config {
  *   key_offset       FME_JOB_BIPRED: element offset of the W*H int16 key block
  *                    (2*org - pred_other, TComYuv::removeHighFreq) in the key buffer
  *                    set by fme_set_keys(); the block is stored row-major with stride W.
+ *                    Range of a key element at bit depth b: -(2^b - 1) .. 2 (2^b - 1)
+ *                    (org and pred_other are samples: -255 .. 510 at 8 bits, -1023 .. 2046 at
+ *                    10), or 0 .. 2^b - 1 when the producer clipped it (FME_PU_CLIP_BIPRED).
+ *                    Every kernel that reads keys is exact over that range and is tested at
+ *                    both ends (tests/test_gpu_stress.py); values outside it are not supported.
  *                    -1: the key is the original picture at (x, y).
  */
 #define FME_JOB_EMI       0x01u  /* run the EMI square step (uni-pred TZ path)           */

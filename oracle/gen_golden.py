@@ -505,9 +505,251 @@ DEEP_CASES = [
 ]
 
 
+# ---- stress content (tests/golden/stress/): saturated, flat and two-level pictures ---------------------
+# In a subdirectory: tests/conftest.py's golden_cases() takes every top-level .npz as a refinement case.
+STRESS_OUT = os.path.join(OUT, "stress")
+STRESS_W, STRESS_H, STRESS_MC_H = 128, 128, 64
+STRESS_LAMBDAS = synth.LDP_LAMBDA[22] + (0.0,)   # slot 4: lambda 0 (the integer search's jobs use it)
+STRESS_REFINE_SETS = ("checker1", "binary", "flat", "twolevel", "full-zero")
+STRESS_TZ_SETS = (("binary", 8), ("checker1", 8), ("flat", 8), ("flat", 32))   # (set, SearchRange)
+STRESS_MC_KINDS = ("binary", "checker1", "full")
+STRESS_KEY_SETS = ("full-zero", "zero-full", "binary")
+STRESS_TEMPLATE_SETS = ("flat", "twolevel", "binary", "checker1")
+
+
+def stress_seeded(name):
+    """Whether a stress set (KIND or ORG-REF) holds a seeded kind: only those planes are stored."""
+    return any(k in synth.STRESS_SEEDED for k in name.split("-"))
+
+
+def save_stress(name, arrays):
+    """An .npz whose bytes depend on the arrays alone (numpy's own writer stamps the time)."""
+    import io
+    import zipfile
+    os.makedirs(STRESS_OUT, exist_ok=True)
+    path = os.path.join(STRESS_OUT, name + ".npz")
+    with zipfile.ZipFile(path, "w") as z:
+        for key in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+    print(f"{path}: {os.path.getsize(path)} bytes, {len(arrays)} arrays")
+
+
+def _stress_engines(pics, keys, bit_depth, **cfg):
+    """(Reference, Oracle) on the same pictures, STRESS_LAMBDAS and keys."""
+    ocfg = dict(cfg)
+    if "nn_mode" in cfg:
+        ocfg["qp"] = 22
+    ref, orc = Reference(bit_depth=bit_depth, **cfg), Oracle(bit_depth=bit_depth, **ocfg)
+    for eng in (ref, orc):
+        for k, v in pics.items():
+            eng.set_picture(k, v)
+        for lid, lam in enumerate(STRESS_LAMBDAS):
+            eng.set_lambda(lid, float(lam))
+        if keys is not None:
+            eng.set_keys(keys if keys.size else np.zeros(1, np.int16))
+        if cfg.get("nn_mode"):
+            eng.load_nn(weights.load_weights(22))
+    return ref, orc
+
+
+def build_stress_refine(bit_depth):
+    """refine: per stress set one batch (synth.stress_refine_batch), HADME 1 and 0, NN on."""
+    out = {"sets": np.array(STRESS_REFINE_SETS), "lambdas": np.array(STRESS_LAMBDAS)}
+    for si, name in enumerate(STRESS_REFINE_SETS):
+        pics = synth.stress_pictures(STRESS_W, STRESS_H, bit_depth, name)
+        # (seed base 704: on `flat` every job then has a tied half and quarter stage at both depths; a
+        # predictor within 2 quarter-pels of the start on both axes makes the centre the only minimum)
+        jobs, keys = synth.stress_refine_batch(np.random.default_rng(704 + 10 * bit_depth + si), STRESS_W, STRESS_H,
+                                               bit_depth, pics)
+        out[f"{name}.jobs"], out[f"{name}.keys"] = jobs, keys
+        if stress_seeded(name):
+            out[f"{name}.pictures"] = np.stack([pics[k] for k in range(5)])
+        for hadme in (1, 0):
+            ref, orc = _stress_engines(pics, keys, bit_depth, use_hadamard=hadme, nn_mode=1, fast_inter_mode=1)
+            r_ref, r_orc = ref.refine(jobs), orc.refine(jobs)
+            bad, first, counts = compare_results(r_ref, r_orc)
+            if bad:
+                raise SystemExit(f"stress refine {name} {bit_depth} bits HADME {hadme}: oracle disagrees with _ref "
+                                 f"on {bad} jobs (first {first}): {counts}")
+            out[f"{name}.results_hadme{hadme}"] = r_ref
+    save_stress(f"refine{bit_depth}", out)
+
+
+def build_stress_tz(bit_depth):
+    """integer_search: per (stress set, SearchRange) one batch (synth.stress_tz_batch), FEN 0 / 1 / 3."""
+    out = {"sets": np.array([f"{n}.sr{sr}" for n, sr in STRESS_TZ_SETS]), "lambdas": np.array(STRESS_LAMBDAS)}
+    for si, (name, sr) in enumerate(STRESS_TZ_SETS):
+        pics = synth.stress_pictures(STRESS_W, STRESS_H, bit_depth, name)
+        jobs, ext, keys = synth.stress_tz_batch(np.random.default_rng(800 + 10 * bit_depth + si), STRESS_W, STRESS_H,
+                                                bit_depth, pics, search_range=sr)
+        case = f"{name}.sr{sr}"
+        out[f"{case}.jobs"], out[f"{case}.ext"], out[f"{case}.keys"] = jobs, ext, keys
+        if stress_seeded(name):
+            out[f"{case}.pictures"] = np.stack([pics[k] for k in range(5)])
+        for fen in (0, 1, 3):
+            ref, orc = _stress_engines(pics, keys, bit_depth, fast_inter_mode=fen)
+            out_r, sad_r = ref.integer_search(jobs, ext)
+            out_o, sad_o = orc.integer_search(jobs, ext)
+            bad = (out_r["mv_x"] != out_o["mv_x"]) | (out_r["mv_y"] != out_o["mv_y"]) | (sad_r != sad_o)
+            if bad.any():
+                raise SystemExit(f"stress tz {case} {bit_depth} bits FEN {fen}: oracle disagrees with _ref on "
+                                 f"{int(bad.sum())} jobs")
+            out[f"{case}.mv_fen{fen}"] = np.stack([out_r["mv_x"], out_r["mv_y"]], axis=1)
+            out[f"{case}.sad_fen{fen}"] = sad_r
+    save_stress(f"tz{bit_depth}", out)
+
+
+def stress_wp_table(rng, refs):
+    """wp_table's extremes: denominators 0 and 7, weights 2^denom - 24 / + 24 / + 0, offsets -128 / 127 / 0."""
+    t = np.zeros((2, refs, 3, 3), np.int32)
+    dl = int(rng.integers(0, 2)) * 7
+    for l in range(2):
+        for r in range(refs):
+            for c in range(3):
+                d = dl if c == 0 else 7 - dl
+                t[l, r, c] = ((1 << d) + (-24, 24, 0)[int(rng.integers(0, 3))], (-128, 127, 0)[int(rng.integers(0, 3))], d)
+    return t
+
+
+def build_stress_mc(bit_depth):
+    """mc: 128x64 4:2:0 references of each kind; uni, bi and explicit WP at wp_table's extremes, MVs
+    out to +-600 quarter-pels (clipMv bites).  The oracle checks all but the 10-bit WP case."""
+    from nnfme.abi import MC_WP
+    W, H = STRESS_W, STRESS_MC_H
+    dt = np.uint16 if bit_depth > 8 else np.uint8
+    out = {"kinds": np.array(STRESS_MC_KINDS), "modes": np.array(["uni", "bi", "wp"])}
+    for ki, kind in enumerate(STRESS_MC_KINDS):
+        pics = synth.stress_yuv(W, H, bit_depth, kind)
+        if stress_seeded(kind):
+            for c, comp in enumerate(("y", "cb", "cr")):
+                out[f"{kind}.ref_{comp}"] = np.stack([pics[k][c] for k in range(3)])
+        for mi, (mode, bi_frac) in enumerate((("uni", 0.0), ("bi", 0.7), ("wp", 0.5))):
+            rng = np.random.default_rng(900 + 100 * bit_depth + 10 * ki + mi)
+            # every CTU split at least once: 128x64 holds two, and two 64x64 PUs would be the whole case
+            jobs = synth.make_mc_partition(rng, W, H, [0, 1, 2], bi_frac=bi_frac, mv_amp=150, identical_frac=0.1,
+                                           p_split=(1.0, 0.7, 0.5))
+            wp = None
+            if mode == "wp":
+                jobs["flags"] = np.where(rng.random(len(jobs)) < 0.8, jobs["flags"] | MC_WP, jobs["flags"])
+                wp = stress_wp_table(rng, 3)
+            ref, orc = Reference(bit_depth=bit_depth), Oracle(bit_depth=bit_depth)
+            for k, v in pics.items():
+                ref.set_picture_yuv(k, *v)
+            if wp is not None:
+                for l in range(2):
+                    for r in range(3):
+                        ref.set_wp(l, r, wp[l, r])
+            planes = [[np.zeros((H, W), dt), np.zeros((H // 2, W // 2), dt), np.zeros((H // 2, W // 2), dt)]
+                      for _ in range(2)]
+            ref.mc(jobs, *planes[0])
+            if wp is None or bit_depth == 8:
+                orc.mc(pics, jobs, *planes[1], wp=wp)
+                for a, b, comp in zip(planes[0], planes[1], "Y Cb Cr".split()):
+                    if not np.array_equal(a, b):
+                        raise SystemExit(f"stress mc {kind} {mode} {bit_depth} bits: oracle disagrees with _ref on "
+                                         f"{comp} ({int((a != b).sum())} samples)")
+            case = f"{kind}.{mode}"
+            out[f"{case}.jobs"] = jobs
+            if wp is not None:
+                out[f"{case}.wp"] = wp
+            for p, comp in zip(planes[0], ("y", "cb", "cr")):
+                out[f"{case}.pred_{comp}"] = p
+    save_stress(f"mc{bit_depth}", out)
+
+
+def build_stress_bi_key(bit_depth):
+    """bi_key: every PU shape twice, all bi-pred, the other list's MV out to +-200 quarter-pels, with
+    and without ClipForBiPredMeEnabled; full against zero and the reverse reach both ends."""
+    out = {"sets": np.array(STRESS_KEY_SETS)}
+    shapes = np.array(synth.ALL_PU_SIZES)
+    for si, name in enumerate(STRESS_KEY_SETS):
+        pics = synth.stress_pictures(STRESS_W, STRESS_H, bit_depth, name)
+        rng = np.random.default_rng(1000 + 10 * bit_depth + si)
+        jobs = synth.make_jobs(rng, STRESS_W, STRESS_H, 48, 4, [0, 1, 2, 3], [0, 1, 2, 3],
+                               sizes=(np.tile(shapes[:, 0], 2), np.tile(shapes[:, 1], 2)))
+        jobs["flags"] = JOB_BIPRED
+        jobs["key_offset"] = -2
+        reqs, count = synth.make_bipred_key_reqs(rng, jobs, 4, [0, 1, 2, 3], mv_span=200)
+        out[f"{name}.jobs"], out[f"{name}.reqs"] = jobs, reqs
+        if stress_seeded(name):
+            out[f"{name}.pictures"] = np.stack([pics[k] for k in range(5)])
+        ref, orc = _stress_engines(pics, None, bit_depth)
+        for clip in (0, 1):
+            keys = np.zeros(count, np.int16)
+            for q in reqs:
+                args = [int(q[f]) for f in ("org_id", "ref_id", "x", "y", "w", "h", "cu_x", "cu_y", "mv_x", "mv_y")]
+                a, b = ref.bi_key(*args, clip), orc.bi_key(*args, clip)
+                if not np.array_equal(a, b):
+                    raise SystemExit(f"stress bi_key {name} {bit_depth} bits clip {clip}: oracle disagrees with _ref")
+                keys[int(q["key_offset"]):int(q["key_offset"]) + a.size] = a.reshape(-1)
+            out[f"{name}.keys_clip{clip}"] = keys
+    save_stress(f"bikey{bit_depth}", out)
+
+
+def stress_template_requests(rng, n, width, height):
+    """CUs at every quadtree depth, every PU shape that fits, two candidates per reference, MVs near
+    and far (clipMv active): tests/test_pred_inter.py's stream on a width x height picture."""
+    from nnfme.abi import PU_REQ_DTYPE
+    reqs = np.zeros(n, dtype=PU_REQ_DTYPE)
+    for i in range(n):
+        w, h = synth.ALL_PU_SIZES[i % len(synth.ALL_PU_SIZES)]
+        cu = max(8, 1 << int(np.ceil(np.log2(max(w, h)))))
+        cu_x, cu_y = cu * int(rng.integers(0, width // cu)), cu * int(rng.integers(0, height // cu))
+        reqs[i]["x"] = cu_x + 4 * int(rng.integers(0, (cu - w) // 4 + 1))
+        reqs[i]["y"] = cu_y + 4 * int(rng.integers(0, (cu - h) // 4 + 1))
+        reqs[i]["w"], reqs[i]["h"], reqs[i]["cu_x"], reqs[i]["cu_y"] = w, h, cu_x, cu_y
+        reqs[i]["depth"] = {64: 0, 32: 1, 16: 2, 8: 3}[cu]
+        reqs[i]["org_id"], reqs[i]["num_refs"], reqs[i]["ref_id"] = 4, 4, [0, 1, 2, 3]
+        reqs[i]["n_cand"] = [2, 2, 1, 2]
+        span = 220 if rng.random() < 0.3 else 40
+        reqs[i]["cand"] = rng.integers(-4 * span, 4 * span + 1, (4, 2, 2))
+        reqs[i]["lambda_id"] = int(rng.integers(0, 4))
+    return reqs
+
+
+def build_stress_template(bit_depth):
+    """template_cost: xGetTemplateCost per (request, reference, candidate) on 128x64 stress sets."""
+    out = {"sets": np.array(STRESS_TEMPLATE_SETS)}
+    for si, name in enumerate(STRESS_TEMPLATE_SETS):
+        pics = synth.stress_pictures(STRESS_W, STRESS_MC_H, bit_depth, name)
+        reqs = stress_template_requests(np.random.default_rng(1100 + 10 * bit_depth + si), 72, STRESS_W, STRESS_MC_H)
+        ref, orc = _stress_engines(pics, None, bit_depth, fast_inter_mode=1)
+        cost = np.full((len(reqs), 4, 2), 0xFFFFFFFF, np.uint32)
+        for i, q in enumerate(reqs):
+            for k in range(4):
+                for m in range(int(q["n_cand"][k])):
+                    mx, my = (int(v) for v in q["cand"][k][m])
+                    cost[i, k, m] = ref.template_cost(4, int(q["ref_id"][k]), int(q["x"]), int(q["y"]), int(q["w"]),
+                                                      int(q["h"]), int(q["cu_x"]), int(q["cu_y"]), mx, my, 1,
+                                                      int(q["lambda_id"]))
+                    if orc.template_cost(q, k, m) != cost[i, k, m]:
+                        raise SystemExit(f"stress template_cost {name} {bit_depth} bits: oracle disagrees with _ref")
+        out[f"{name}.reqs"], out[f"{name}.cost"] = reqs, cost
+        if stress_seeded(name):
+            out[f"{name}.pictures"] = np.stack([pics[k] for k in range(5)])
+    save_stress(f"template{bit_depth}", out)
+
+
+def build_stress():
+    for bit_depth in (8, 10):
+        build_stress_refine(bit_depth)
+        build_stress_tz(bit_depth)
+        build_stress_mc(bit_depth)
+        build_stress_bi_key(bit_depth)
+        build_stress_template(bit_depth)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
-    only = sys.argv[sys.argv.index("--only") + 1].split(",") if "--only" in sys.argv else None
+    if "--stress-only" in sys.argv:
+        build_stress()
+        return 0
+    only =sys.argv[sys.argv.index("--only") + 1].split(",") if "--only" in sys.argv else None
     if only:
         for c in CASES + DEEP_CASES:
             if c[0] in only:
@@ -561,6 +803,8 @@ def main():
         build_tz2_case(*c)
     for c in TZ10_CASES:
         build_tz10_case(*c)
+    if "--mc-only" not in sys.argv and "--tz-only" not in sys.argv:
+        build_stress()
     return 0
 
 
