@@ -28,7 +28,8 @@ thread_local std::string g_last_error = "";
 // invalid and keyed counts, and the 8 lane tile-queue heads), all zeroed at allocation.  Batch k
 // counts in block k % kOvBlocks and its k_front (the workgroup that finishes last) zeroes the block
 // of batch k + 2: no fill dispatch per batch, and no block is zeroed while the batch before or
-// after, which may run beside this one on another stream, uses it (fme_overlap_host.h).  Whatever
+// after, whose front end and search may run beside this one's on another stream, uses it
+// (fme_overlap_host.h).  Whatever
 // else touches the blocks (the integer search, a batch whose launches failed midway) leaves them
 // in doubt (OverlapState::dirty), and the next batch starts, behind every batch in flight, with
 // one hipMemsetAsync of all blocks.
@@ -63,14 +64,15 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
   std::unique_ptr<fme_ctx> c(new fme_ctx());
   c->device = device;
   c->cfg = *cfg;
-  HIP_TRY(c->d_pics.reserve(kOvSlots * FME_MAX_PICTURES));
-  HIP_TRY(c->d_mlambda.reserve(kOvSlots * FME_MAX_LAMBDAS));
+  HIP_TRY(c->d_pics.reserve((1 + kOvRing) * FME_MAX_PICTURES));
+  HIP_TRY(c->d_mlambda.reserve((1 + kOvRing) * FME_MAX_LAMBDAS));
   HIP_TRY(c->d_nn.reserve(kNnPkFloats));
   HIP_TRY(c->counts.reserve(kOvBlocks * kCountWords));
   HIP_TRY(hipMemset(c->counts.p, 0, kOvBlocks * kCountWords * sizeof(int32_t)));
-  HIP_TRY(c->d_sched.reserve(kOvSlots));
-  HIP_TRY(hipMemset(c->d_sched.p, 0, kOvSlots * sizeof(Schedule)));
+  HIP_TRY(c->d_sched.reserve(kOvRing));
+  HIP_TRY(hipMemset(c->d_sched.p, 0, kOvRing * sizeof(Schedule)));
   for (auto& e : c->done_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& e : c->search_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   c->sched_p = sched_params();
   {
     const char* m10 = std::getenv("FME_MAIN10_SEARCH");
@@ -88,8 +90,10 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
     for (int b = 0; b < kOvSlots; b++) {
       HIP_TRY(c->cls[b].reserve(n));
       HIP_TRY(c->perm[b].reserve(n * kNumClasses));   // one region of n jobs per class (k_front)
-      HIP_TRY(c->blk_agg[b].reserve(nb * 9));
-      HIP_TRY(c->blk_prefix[b].reserve(nb * 9));
+    }
+    for (int r = 0; r < kOvRing; r++) {
+      HIP_TRY(c->blk_agg[r].reserve(nb * 9));
+      HIP_TRY(c->blk_prefix[r].reserve(nb * 9));
     }
   }
   *out_ctx = c.release();
@@ -98,15 +102,22 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
 
 }  // extern "C"
 static int srv_stop(fme_ctx* c);
-// The end event of the batch `back` batches ago (1: the last one), or null.
+// The end event of the batch `back` batches ago (1: the last one), or null; search_event: the
+// event behind its search launch.
 static hipEvent_t done_event(const fme_ctx* c, int back) {
-  if (back < 1 || back > 2 || !c->ov.live[back - 1]) return nullptr;
+  if (back < 1 || back > kOvBack || !c->ov.live[back - 1]) return nullptr;
   return c->done_ev[(c->ov.seq - back) % fme_ctx::kDoneRing];
 }
-// s waits for the refinement batches in flight on other streams (at most two: a batch's tail waits
-// for the batch before it).
+static hipEvent_t search_event(const fme_ctx* c, int back) {
+  if (back < 1 || back > kOvBack || !c->ov.live[back - 1]) return nullptr;
+  return c->search_ev[(c->ov.seq - back) % fme_ctx::kDoneRing];
+}
+// s waits for the refinement batches in flight on other streams: at most three (the search of a
+// batch waits for the end of the batch two before it, so the tail of batch k - 3 may be pending
+// when batch k is planned).  A batch's end event fires after its search-end event, on the same
+// stream: it covers both.
 static int wait_batches(fme_ctx* c, hipStream_t s) {
-  for (int back = 1; back <= 2; back++)
+  for (int back = 1; back <= kOvBack; back++)
     if (hipEvent_t e = done_event(c, back))
       if (c->ov.stream[back - 1] != s) HIP_TRY(hipStreamWaitEvent(s, e, 0));
   return FME_OK;
@@ -173,11 +184,16 @@ int fme_destroy(fme_ctx* c) {
   c->d_pics.release(); c->d_mlambda.release(); c->d_keys.release(); c->d_nn.release(); c->d_net.release();
   c->d_jobs.release(); c->d_res.release(); c->d_res1.release(); c->d_mv.release();
   for (int b = 0; b < kOvSlots; b++) {
-    c->koff[b].release(); c->cls[b].release(); c->perm[b].release(); c->blk_agg[b].release(); c->blk_prefix[b].release();
+    c->cls[b].release(); c->perm[b].release();
+  }
+  for (int r = 0; r < kOvRing; r++) {
+    c->koff[r].release(); c->blk_agg[r].release(); c->blk_prefix[r].release();
   }
   c->counts.release(); c->nn_state.release();
   c->d_sched.release();
   for (auto& e : c->done_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->search_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->state_read_ev)
     if (e) (void)hipEventDestroy(e);
@@ -475,8 +491,10 @@ int fme_nn_copy_state_device(fme_ctx* c, uint32_t* d_out12, void* stream) {
 // perm holds one region per PU class, each as long as the context's job capacity (k_front writes
 // class c's jobs from c * capacity on, whatever the batch's class totals turn out to be): 96 bytes
 // per job of capacity, 83 MB for a 1080p frame's 862,920 jobs; and that once per batch slot.
-// Both slots are sized together.  *grows (may be null): a buffer had to grow (freeing the old one
-// waits for the device, so no batch in flight loses a buffer it reads).
+// The ring entries (fme_overlap_host.h) hold what the tail still reads: koff, 4 bytes per job of
+// capacity, and the scan blocks' 72 bytes per 1,024 jobs; 3.5 MB per entry for that frame.
+// All slots and entries are sized together.  *grows (may be null): a buffer had to grow (freeing
+// the old one waits for the device, so no batch in flight loses a buffer it reads).
 static int ensure_work(fme_ctx* c, int n, bool* grows = nullptr) {
   const size_t nb = ((size_t)n + kJobsPerScanBlock - 1) / kJobsPerScanBlock;
   if ((size_t)n * kNumClasses > (size_t)INT32_MAX) return fail(FME_E_INVALID, "%d jobs in one batch", n);
@@ -484,29 +502,32 @@ static int ensure_work(fme_ctx* c, int n, bool* grows = nullptr) {
   for (int b = 0; b < kOvSlots; b++) {
     HIP_TRY(c->cls[b].reserve(n));
     HIP_TRY(c->perm[b].reserve((size_t)n * kNumClasses));
-    HIP_TRY(c->blk_agg[b].reserve(nb * 9));
-    HIP_TRY(c->blk_prefix[b].reserve(nb * 9));
-    HIP_TRY(c->koff[b].reserve(n));
+  }
+  for (int r = 0; r < kOvRing; r++) {
+    HIP_TRY(c->blk_agg[r].reserve(nb * 9));
+    HIP_TRY(c->blk_prefix[r].reserve(nb * 9));
+    HIP_TRY(c->koff[r].reserve(n));
   }
   return FME_OK;
 }
 
-// The work buffers of slot `slot`, counting in counter block `block`; the front end's last
-// workgroup zeroes block `zeroed`.
-static WorkBufs work_bufs(fme_ctx* c, int slot, int block, int zeroed) {
+// The work buffers of a planned batch: its slot's perm and cls, its ring entry's koff, scan blocks
+// and Schedule, counting in its counter block; the front end's last workgroup zeroes the block
+// the plan names.
+static WorkBufs work_bufs(fme_ctx* c, const OverlapPlan& plan) {
   WorkBufs w{};
-  w.cls = c->cls[slot].p;
-  w.perm = c->perm[slot].p;
-  w.perm_cap = (int32_t)(c->perm[slot].cap / kNumClasses);
-  w.koff = c->koff[slot].p;
-  w.counts = c->counts.p + block * kCountWords;
-  w.counts_next = c->counts.p + zeroed * kCountWords;
+  w.cls = c->cls[plan.slot].p;
+  w.perm = c->perm[plan.slot].p;
+  w.perm_cap = (int32_t)(c->perm[plan.slot].cap / kNumClasses);
+  w.koff = c->koff[plan.ring].p;
+  w.counts = c->counts.p + plan.block * kCountWords;
+  w.counts_next = c->counts.p + plan.block_zeroed * kCountWords;
   w.cursor = w.counts + kCursorWord;
   w.tile_ctr = w.counts + kTileCtrWord;
-  w.blk_agg = c->blk_agg[slot].p;
-  w.blk_prefix = c->blk_prefix[slot].p;
+  w.blk_agg = c->blk_agg[plan.ring].p;
+  w.blk_prefix = c->blk_prefix[plan.ring].p;
   w.nn_state = c->nn_state.p;
-  w.sched = c->d_sched.p + slot;
+  w.sched = c->d_sched.p + plan.ring;
   w.mv_out = nullptr;
   return w;
 }
@@ -525,21 +546,28 @@ BatchArgs fme::batch_args(const fme_ctx* c, const fme_job* jobs, int n) {
   return a;
 }
 
-// The picture / lambda tables go to the device in stream order as the argument of a one-block
-// kernel: rebinding pictures for the next frame never waits for the batch in flight, and the
-// batch stream holds no copy-engine transfer (which would queue behind bulk uploads).
-// Slot `slot`'s copy is brought up to date when the host tables changed since its last upload (a
-// batch's slot: its previous user is over before this launch, refine_batch's slot wait).
-static int put_tables(fme_ctx* c, int slot, hipStream_t s) {
-  note_stream(c, s);   // every batch entry point passes here with its stream
+// What every batch entry point does with its stream before it enqueues anything.
+static int enter_stream(fme_ctx* c, hipStream_t s) {
+  note_stream(c, s);
   // a resident server could hold up this work on a hardware queue its stream shares: stop it
   // (a few microseconds; the next single call relaunches it)
-  FME_TRY(srv_stop(c));
+  return srv_stop(c);
+}
+
+// The picture / lambda tables go to the device in stream order, never through a copy engine:
+// rebinding pictures for the next frame never waits for the batch in flight, and the batch stream
+// holds no copy-engine transfer (which would queue behind bulk uploads).  A refinement batch
+// carries them in k_front's kernel argument, and k_front writes the batch's ring entry's copy
+// (refine_batch).  Everything else reads copy 0, which a one-block kernel brings up to date here
+// when the host tables changed since its last upload; its readers are over before this launch
+// (sync_tables waits for the batches in flight, and those read their ring entries' copies).
+static int put_tables(fme_ctx* c, hipStream_t s) {
+  FME_TRY(enter_stream(c, s));
   if (c->tables_dirty) {
     c->tab_gen++;
     c->tables_dirty = false;
   }
-  if (c->slot_gen[slot] == c->tab_gen) return FME_OK;
+  if (c->shared_gen == c->tab_gen) return FME_OK;
   if (!c->h_tab) {
     void* p = nullptr;
     HIP_TRY(hipHostMalloc(&p, fme_ctx::kTabSlots * sizeof(TablesSlot), hipHostMallocMapped));
@@ -554,31 +582,40 @@ static int put_tables(fme_ctx* c, int slot, hipStream_t s) {
   if (c->tab_used[k]) HIP_TRY(hipEventSynchronize(c->tab_ev[k]));   // its last launch has run
   std::memcpy(c->h_tab[k].pics, c->pics, sizeof(c->pics));
   std::memcpy(c->h_tab[k].ml, c->mlambda, sizeof(c->mlambda));
-  HIP_TRY(launch_put_tables(c->d_pics.p + slot * FME_MAX_PICTURES, c->d_mlambda.p + slot * FME_MAX_LAMBDAS,
-                            c->h_tab_dev + k, s));
+  HIP_TRY(launch_put_tables(c->d_pics.p, c->d_mlambda.p, c->h_tab_dev + k, s));
   HIP_TRY(hipEventRecord(c->tab_ev[k], s));
   c->tab_used[k] = true;
-  c->slot_gen[slot] = c->tab_gen;
+  c->shared_gen = c->tab_gen;
   return FME_OK;
 }
 
 int fme::sync_tables(fme_ctx* c, hipStream_t s) {
   FME_TRY(wait_batches(c, s));
-  return put_tables(c, 0, s);
+  return put_tables(c, s);
 }
 
-// What a planned batch (or integer search) does before its first launch: its end event, the waits
-// of its plan, and the fill of the counter blocks when they are in doubt.
-static int batch_begin(fme_ctx* c, const OverlapPlan& plan, hipStream_t s, hipEvent_t* done) {
-  hipEvent_t const prev_done = done_event(c, 1), slot_done = done_event(c, 2);
-  // this batch's end event: recorded once per use; before an entry of the ring is recorded again,
-  // the waits queued on its last record (by the two batches after that one) have been passed,
-  // which the end of the later of the two says
+// What a planned batch (or integer search) does before its first launch: its two events, the waits
+// of its plan that come before the front end, and the fill of the counter blocks when they are in
+// doubt.
+static int batch_begin(fme_ctx* c, const OverlapPlan& plan, hipStream_t s, hipEvent_t* search_end, hipEvent_t* done) {
+  // this batch's events: recorded once per use; before an entry of a ring is recorded again, the
+  // waits queued on its last record (by the three batches after that one) have been passed, which
+  // the end of the last of the three says
+  *search_end = c->search_ev[c->ov.seq % fme_ctx::kDoneRing];
   *done = c->done_ev[c->ov.seq % fme_ctx::kDoneRing];
   if (c->ov.seq >= fme_ctx::kDoneRing)
-    HIP_TRY(hipEventSynchronize(c->done_ev[(c->ov.seq + 2) % fme_ctx::kDoneRing]));
-  if (plan.wait_prev_front) HIP_TRY(hipStreamWaitEvent(s, prev_done, 0));
-  if (plan.wait_slot) HIP_TRY(hipStreamWaitEvent(s, slot_done, 0));
+    HIP_TRY(hipEventSynchronize(c->done_ev[(c->ov.seq + kOvBack) % fme_ctx::kDoneRing]));
+  if (plan.serial) {   // behind every batch in flight
+    if (plan.wait_prev_front) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 1), 0));
+    if (plan.wait_slot) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 2), 0));
+    if (plan.wait_back3) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 3), 0));
+  } else if (plan.wait_front) {
+    // search k - 2 is over: perm and cls of the slot and its counter block are free; the tail of
+    // batch k - 2 may be pending, it reads its own ring entry
+    HIP_TRY(hipStreamWaitEvent(s, search_event(c, 2), 0));
+  } else if (plan.wait_front_end) {
+    HIP_TRY(hipStreamWaitEvent(s, done_event(c, 2), 0));   // batch k - 2 was serialised: all of it
+  }
   // The counter block is zero: batch k - 2's k_front left it so (the first batches' blocks
   // fme_create zeroed).  After a batch that was abandoned on the host half-way all blocks are
   // filled here.  Its launches carry no end event, so the host waits for the context's streams
@@ -654,22 +691,30 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
                             (c->cfg.bit_depth > 8 && c->main10_px ? kOvPx : 0u) |
                             (d_jobs && d_jobs == c->d_jobs.p ? kOvStaged : 0u) | (grows ? kOvGrow : 0u);
   const OverlapPlan plan = overlap_plan(c->ov, s, features);
-  hipEvent_t const prev_done = done_event(c, 1);
-  hipEvent_t done = nullptr;
-  FME_TRY(batch_begin(c, plan, s, &done));
-  FME_TRY(put_tables(c, plan.slot, s));
+  hipEvent_t const prev_done = done_event(c, 1), slot_done = done_event(c, 2);
+  hipEvent_t search_end = nullptr, done = nullptr;
+  FME_TRY(enter_stream(c, s));
+  FME_TRY(batch_begin(c, plan, s, &search_end, &done));
 
+  // The batch's picture / lambda tables travel in k_front's kernel argument; k_front validates
+  // against them and writes them to the ring entry's device copy, which the search and the tail read.
+  PicDesc* const d_pics = c->d_pics.p + (1 + plan.ring) * FME_MAX_PICTURES;
+  double* const d_ml = c->d_mlambda.p + (1 + plan.ring) * FME_MAX_LAMBDAS;
+  BatchTables tab;
+  for (int i = 0; i < FME_MAX_PICTURES; i++)
+    tab.pics[i] = BatchPic{c->pics[i].luma, c->pics[i].stride, c->pics[i].width, c->pics[i].height, 0};
+  std::memcpy(tab.ml, c->mlambda, sizeof(c->mlambda));
   BatchArgs a = batch_args(c, d_jobs, n);
-  a.pics = c->d_pics.p + plan.slot * FME_MAX_PICTURES;
-  a.mlambda = c->d_mlambda.p + plan.slot * FME_MAX_LAMBDAS;
+  a.pics = d_pics;
+  a.mlambda = d_ml;
   a.pjobs = d_jobs ? nullptr : d_pjobs;
   a.key_base = d_key_base;
-  a.koff = c->koff[plan.slot].p;
+  a.koff = c->koff[plan.ring].p;
   a.res = d_res;
   a.nn_mode = c->cfg.nn_mode ? 1 : 0;
   a.nn_in = c->nn_in;
   a.nn_in_cap = c->nn_in_cap;
-  WorkBufs w = work_bufs(c, plan.slot, plan.block, plan.block_zeroed);
+  WorkBufs w = work_bufs(c, plan);
   w.mv_out = d_mv;
 
   const bool prof = c->profiling;
@@ -688,8 +733,10 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
   // the counter block is zero (batch_begin); the blocks stay in doubt until every launch of the
   // batch is enqueued (overlap_commit)
   overlap_begin(c->ov);
-  HIP_TRY(launch_front(a, w, c->sched_p, s));
+  HIP_TRY(launch_front(a, w, c->sched_p, tab, d_pics, d_ml, s));
   if (prof) HIP_TRY(hipEventRecord(ev[3], s));
+  // the search writes the slot's internal records, which the tail of batch k - 2 reads
+  if (plan.wait_search) HIP_TRY(hipStreamWaitEvent(s, slot_done, 0));
   if (c->ev_search) HIP_TRY(hipEventRecord(c->ev_search, s));
   // the lane kernel: every PU shape, one launch on the batch stream (8-bit); the pixel kernel at
   // bit depth 10 (fme_px.hip)
@@ -705,6 +752,7 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
     HIP_TRY(launch_search_lane(a, w, c->search_reserve, s));
   }
   if (prof) HIP_TRY(hipEventRecord(ev[4], s));
+  HIP_TRY(hipEventRecord(search_end, s));   // what the front end of batch k + 2 waits for
   // the tails hand the NN state on: this one runs after the previous batch's, the one dependency
   // between consecutive batches; a reset / set of the state belongs between the two
   if (plan.wait_prev_tail) HIP_TRY(hipStreamWaitEvent(s, prev_done, 0));
@@ -713,10 +761,11 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
     c->state_read_last = nullptr;
   }
   FME_TRY(apply_pending_state(c, s));
-  // (The tail stays on the batch's stream.  Where it becomes runnable a few microseconds after the
-  // next batch's search, that search's persistent workgroups hold every wave slot and the tail runs
-  // as they drain; on a stream of the highest priority it did the same, since resident workgroups
-  // are not displaced: DESIGN.md section 5 "Batch overlap".)
+  // (The tail stays on the batch's stream.  Where it becomes runnable after the next batch's search
+  // has started, that search's persistent workgroups hold every wave slot and the tail runs as they
+  // drain; on a stream of the highest priority it did the same, since resident workgroups are not
+  // displaced: DESIGN.md section 5 "Batch overlap".  The front end of batch k + 2 does not wait for
+  // it: it reads this batch's ring entry, the front end writes another.)
   if (prof) HIP_TRY(hipEventRecord(ev[5], s));
   HIP_TRY(c->cfg.nn_mode == 2
               ? launch_nn_deep_tail(c->net, c->d_net.p, c->nn_margin, c->nn_logits, a, w, c->state_cur, c->nn_engine, s)
@@ -728,6 +777,7 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
   HIP_TRY(hipEventRecord(done, s));
   c->ev_done = done;
   c->last_slot = plan.slot;
+  c->last_ring = plan.ring;
   c->keys_fresh = false;
   overlap_commit(c->ov, s, features, plan);
   c->batch_issued = true;
@@ -737,7 +787,7 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
 
 // After a refinement batch: the rejected-job count comes down, one synchronisation, FME_E_INVALID if any.
 int fme::check_rejected(fme_ctx* c, hipStream_t s, const char* name, const char* what) {
-  HIP_TRY(hipMemcpyAsync(c->h_counts, &c->d_sched.p[c->last_slot].invalid, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(c->h_counts, &c->d_sched.p[c->last_ring].invalid, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (c->h_counts[0] > 0)
     return fail(FME_E_INVALID, "%s: %d job(s) %s", name, c->h_counts[0], what);
@@ -1024,7 +1074,7 @@ int fme_refine_status(fme_ctx* c) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipEventSynchronize(c->ev_done));
   int32_t v = 0;
-  HIP_TRY(hipMemcpy(&v, &c->d_sched.p[c->last_slot].invalid, sizeof(v), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&v, &c->d_sched.p[c->last_ring].invalid, sizeof(v), hipMemcpyDeviceToHost));
   return v;
 }
 
@@ -1042,7 +1092,7 @@ int fme_debug_front(fme_ctx* c, int32_t* perm_out, long long perm_words, int32_t
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipEventSynchronize(c->ev_done));
   if (perm_out && perm_words) HIP_TRY(hipMemcpy(perm_out, c->perm[c->last_slot].p, (size_t)perm_words * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (sched_out && sched_words) HIP_TRY(hipMemcpy(sched_out, c->d_sched.p + c->last_slot, (size_t)sched_words * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (sched_out && sched_words) HIP_TRY(hipMemcpy(sched_out, c->d_sched.p + c->last_ring, (size_t)sched_words * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (cap_out) *cap_out = (int32_t)(c->perm[c->last_slot].cap / kNumClasses);
   return FME_OK;
 }
@@ -1084,11 +1134,12 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   // The integer search is planned like a refinement batch (kOvForeign): behind every batch in
   // flight, with a batch number of its own, so that its slot and counter block are nobody else's,
   // the block comes round zeroed again (its scatter zeroes the block of the batch after next, as
-  // k_front does) and the batches after it wait for its end event.  It reads slot 0's tables.
+  // k_front does) and the batches after it wait for its events, both recorded at its end.  It
+  // reads copy 0 of the tables.
   const OverlapPlan plan = overlap_plan(c->ov, s, kOvForeign);
-  hipEvent_t done = nullptr;
-  FME_TRY(batch_begin(c, plan, s, &done));
-  WorkBufs w = work_bufs(c, plan.slot, plan.block, plan.block_zeroed);
+  hipEvent_t search_end = nullptr, done = nullptr;
+  FME_TRY(batch_begin(c, plan, s, &search_end, &done));
+  WorkBufs w = work_bufs(c, plan);
   if (c->profiling) {
     if (!c->ev_tz[0]) {
       HIP_TRY(hipEventCreate(&c->ev_tz[0]));
@@ -1155,6 +1206,7 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   HIP_TRY(hipStreamWaitEvent(s, c->ev_join2, 0));
   if (c->profiling) HIP_TRY(hipEventRecord(c->ev_tz[1], s));
   c->tz_timed = c->profiling;
+  HIP_TRY(hipEventRecord(search_end, s));
   HIP_TRY(hipEventRecord(done, s));
   overlap_commit(c->ov, s, kOvForeign, plan);
   return FME_OK;

@@ -94,14 +94,16 @@ struct fme_ctx {
   bool lambda_set[FME_MAX_LAMBDAS]{};
   bool tables_dirty = true;
 
-  // The device tables, one copy per batch slot (fme_overlap_host.h): slot b's at d_pics.p +
-  // b * FME_MAX_PICTURES and d_mlambda.p + b * FME_MAX_LAMBDAS.  Everything but the refinement
-  // batches reads slot 0 (sync_tables).  tab_gen counts the host tables' changes, slot_gen[b] is
-  // the change slot b holds.
+  // The device tables, 1 + kOvRing copies, copy t at d_pics.p + t * FME_MAX_PICTURES and
+  // d_mlambda.p + t * FME_MAX_LAMBDAS.  Copy 0 is what everything but the refinement batches
+  // reads (sync_tables: behind every batch in flight); copy 1 + r belongs to ring entry r
+  // (fme_overlap_host.h) and is written by the k_front of every batch that has the entry, from
+  // its kernel argument.  tab_gen counts the host tables' changes, shared_gen is the change copy 0
+  // holds.
   fme::DevBuf<fme::PicDesc> d_pics;
   fme::DevBuf<double> d_mlambda;
-  unsigned long long tab_gen = 1, slot_gen[fme::kOvSlots] = {};
-  // the tables' upload ring (sync_tables): pinned, device-mapped slots, each guarded by the event of
+  unsigned long long tab_gen = 1, shared_gen = 0;
+  // copy 0's upload ring (sync_tables): pinned, device-mapped slots, each guarded by the event of
   // the launch that reads it
   static constexpr int kTabSlots = 16;
   fme::TablesSlot* h_tab = nullptr;
@@ -129,30 +131,34 @@ struct fme_ctx {
   fme::DevBuf<fme_result> d_res;
   fme::DevBuf<fme_result> d_res1;    // the *_mv_* device entry points' records of a batch in slot 1
   fme::DevBuf<fme_mv_result> d_mv;   // staging for fme_refine_mv
-  // What a batch's kernels hand each other, one set per batch slot (consecutive batches on two
-  // streams overlap: fme_overlap_host.h); the integer search takes a batch number and its slot.
-  fme::DevBuf<int32_t> koff[fme::kOvSlots];   // packed batches: key offset per keyed job (k_classify)
+  // What a batch's kernels hand each other (consecutive batches on two or three streams overlap:
+  // fme_overlap_host.h); the integer search takes a batch number and with it a slot and a ring entry.
+  // Per slot: what only the front end and the search touch.  Per ring entry: what the tail still reads.
   fme::DevBuf<uint8_t> cls[fme::kOvSlots];
   fme::DevBuf<int32_t> perm[fme::kOvSlots];
-  fme::DevBuf<int32_t> blk_agg[fme::kOvSlots];
-  fme::DevBuf<int32_t> blk_prefix[fme::kOvSlots];
+  fme::DevBuf<int32_t> koff[fme::kOvRing];    // packed batches: key offset per keyed job (k_front)
+  fme::DevBuf<int32_t> blk_agg[fme::kOvRing];
+  fme::DevBuf<int32_t> blk_prefix[fme::kOvRing];
   fme::DevBuf<int32_t> counts;      // kOvBlocks counter blocks (kCountWords each), used in rotation
-  fme::OverlapState ov;             // batch count, the last two batches' streams, blocks in doubt
-  // the batches' end events: batch k records done_ev[k % kDoneRing] once, after its tail
+  fme::OverlapState ov;             // batch count, the last three batches' streams, blocks in doubt
+  // the batches' events: batch k records search_ev[k % kDoneRing] behind its search launch and
+  // done_ev[k % kDoneRing] after its tail, each once
   static constexpr int kDoneRing = 16;
   hipEvent_t done_ev[kDoneRing] = {};
+  hipEvent_t search_ev[kDoneRing] = {};
   // fme_nn_copy_state_device's reads of the carried state: the next batch's set / reset waits for the latest
   hipEvent_t state_read_ev[kDoneRing] = {};
   long long state_reads = 0;
   hipEvent_t state_read_last = nullptr;
   hipStream_t state_read_stream = nullptr;
-  int last_slot = 0;                // slot of the last batch (fme_refine_status, fme_debug_front)
+  int last_slot = 0;                // slot and ring entry of the last batch (fme_refine_status, fme_debug_front)
+  int last_ring = 0;
   bool keys_fresh = false;          // the key buffer was written since the last batch
   fme::DevBuf<uint32_t> nn_state;   // 2 x 12 words
   int state_cur = 0;
   bool state_pending = false;   // reset / set_state not yet applied (next batch, stream order)
   uint32_t pending_state[12] = {};
-  fme::DevBuf<fme::Schedule> d_sched;     // [kOvSlots], built by k_front each batch
+  fme::DevBuf<fme::Schedule> d_sched;     // [kOvRing], built by k_front each batch
   fme::SchedParams sched_p{};
   int32_t* h_counts = nullptr; // pinned
 

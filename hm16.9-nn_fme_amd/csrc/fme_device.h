@@ -19,6 +19,11 @@ constexpr int kNumClasses = 24;      // HEVC inter PU shapes 4x8 .. 64x64 incl. 
 // 0 = by class id (smallest PUs first), 1 = reversed (largest first), 2 = smallest and largest
 // alternating (0, 23, 1, 22, ...).  A/B on the 1080p batch: 0.876 / 0.880 / 0.884 ms, results
 // identical (profiles/r06_ab.log): the band's first class pays its cold start whichever it is.
+// Orders 0 and 1 both end with a class whose tiles are among the longest (64x64, 4x8).  An order
+// with the costly classes first and the cheapest last (64x64, 48x64, 64x48, 4x8, 4x16, 8x4, then
+// by falling cycles per tile of profiles/r06_lane_phase_stamps.txt) was built in round 13 and
+// removed again: in the overlapped layout its headline runs fell into two groups, 1.020 - 1.039
+// and 1.061 - 1.072 ms per step, against 1.018 - 1.042 for order 0 (profiles/r13_bench_headline.txt).
 #ifndef FME_LANE_ORDER
 #define FME_LANE_ORDER 0
 #endif
@@ -298,10 +303,32 @@ struct TzChain {
 hipError_t launch_tz_levels(const TzArgs& ta, const TzChain& ch, const int32_t* h_lvl_off, int bit_depth, hipStream_t s);
 
 // Host-side launch helpers (fme_kernels.hip).
-// A refinement batch's front end in one pass: validation, class, perm (class c at c * w.perm_cap),
-// the NN writer maxima; the workgroup that finishes last writes *w.sched (block ranges, XCD queues,
-// invalid count) and w.blk_prefix and zeroes w.counts_next
-hipError_t launch_front(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, hipStream_t s);
+// The picture / lambda tables as k_put_tables copies them from a pinned, device-mapped host slot
+// (everything but a refinement batch).
+struct TablesSlot {
+  PicDesc pics[FME_MAX_PICTURES];
+  double ml[FME_MAX_LAMBDAS];
+};
+// A refinement batch's tables as k_front's kernel argument: of each picture what the refinement
+// kernels read, the luma plane (the chroma planes are motion compensation's and the skip check's,
+// which read the shared device copy), so that the argument is 2 KB where the whole PicDesc table,
+// 3.5 KB, would not fit the 4 KB argument segment beside the other arguments.
+struct BatchPic {
+  const uint8_t* luma;
+  int32_t stride, width, height;
+  int32_t pad_;
+};
+struct BatchTables {
+  BatchPic pics[FME_MAX_PICTURES];
+  double ml[FME_MAX_LAMBDAS];
+};
+// A refinement batch's front end in one pass: validation (against t), class, perm (class c at
+// c * w.perm_cap), the NN writer maxima; its first workgroup writes t to d_pics / d_ml (what a.pics
+// and a.mlambda name for the search and the tail; chroma fields null); the workgroup that finishes
+// last writes *w.sched (block ranges, XCD queues, invalid count) and w.blk_prefix and zeroes
+// w.counts_next
+hipError_t launch_front(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, const BatchTables& t,
+                        PicDesc* d_pics, double* d_ml, hipStream_t s);
 // The integer search's two passes (its class offsets are dense):
 // validation, class and the class histogram in w.counts,
 hipError_t launch_classify(const BatchArgs& a, const WorkBufs& w, hipStream_t s);
@@ -310,12 +337,7 @@ hipError_t launch_classify(const BatchArgs& a, const WorkBufs& w, hipStream_t s)
 hipError_t launch_scatter(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, hipStream_t s);
 // 12 words of NN state written to dst in stream order (reset / set_state)
 hipError_t launch_put_state(uint32_t* dst, const uint32_t* v12, hipStream_t s);
-// the picture / lambda tables written in stream order from kernel arguments
-// One batch's picture / lambda tables (a pinned, device-mapped host slot; k_put_tables copies it).
-struct TablesSlot {
-  PicDesc pics[FME_MAX_PICTURES];
-  double ml[FME_MAX_LAMBDAS];
-};
+// the picture / lambda tables written in stream order from a pinned, device-mapped host slot
 hipError_t launch_put_tables(PicDesc* d_pics, double* d_ml, const TablesSlot* t_dev, hipStream_t s);
 // The search kernel reads its schedule from *w.sched (no host round trip); it is launched with
 // enough workgroups to fill the chip, each pulling tiles from its XCD's queue (then the other

@@ -1,6 +1,7 @@
 // fme_kernels.hip — CDNA4 (gfx950) kernels of the fractional-pel motion-estimation path.
 //
-// One batch of PU jobs runs as four launches (tables, front, search, nn_tail).  The
+// One batch of PU jobs runs as three launches (front, search, nn_tail; the picture / lambda tables
+// travel in the front end's kernel argument).  The
 // jobs are read where the caller put them, through load_job (fme_device.h): fme_job rows, or the
 // 16-byte fme_job_packed rows of the packed entry points expanded in registers; no kernel writes
 // an unpacked copy.
@@ -133,12 +134,14 @@ __device__ __forceinline__ void front_load(const BatchArgs& a, const WorkBufs& w
 }
 
 // The class table, the picture sizes and the key flag, one entry per lane (before the workgroup's barrier).
-__device__ __forceinline__ void front_tables(const BatchArgs& a, FrontTables& T) {
+// pics: the batch's picture table (PicDesc: the device copy; BatchPic: k_front's kernel argument).
+template <class Pic>
+__device__ __forceinline__ void front_tables(const BatchArgs& a, const Pic* pics, FrontTables& T) {
   const int tid = threadIdx.x;
   if (tid == 0) T.keys_bad = a.key_invalid ? *a.key_invalid : 0;
   T.lut[tid] = kClassLut.v[tid];
   if (tid < FME_MAX_PICTURES) {
-    const PicDesc p = a.pics[tid];
+    const Pic p = pics[tid];
     T.pic_w[tid] = p.luma ? p.width : -1;
     T.pic_h[tid] = p.height;
   }
@@ -183,7 +186,7 @@ __global__ __launch_bounds__(kBlock) void k_classify(BatchArgs a, WorkBufs w) {
   const int base = blockIdx.x * kJobsPerScanBlock;
   fme_job jb[kFrontQ];
   front_load(a, w, base, jb);
-  front_tables(a, T);
+  front_tables(a, a.pics, T);
   if (tid == 0) keyed = 0;
   if (tid < kNumClasses + 1) hist[tid] = 0;
   if (tid < 9) agg[tid] = -1;
@@ -339,7 +342,18 @@ __device__ __forceinline__ void front_blk_prefix(const WorkBufs& w, int nb) {
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_front(BatchArgs a, WorkBufs w, SchedParams sp) {
+// The batch's picture / lambda tables are the kernel argument tab (2 KB: fme_device.h BatchTables;
+// with the other arguments and the hidden ones 2.6 KB of the 4 KB argument segment, checked
+// below): every workgroup validates against the argument, so none waits for the device copy, and
+// the first workgroup writes that copy (d_pics, d_ml: the batch's ring entry) for the search and
+// the tail, which follow in stream order.  No launch of its own carries the tables (k_put_tables
+// did: one workgroup that queued for a wave slot behind the search before the front end could
+// follow it).
+static_assert(sizeof(BatchArgs) + sizeof(WorkBufs) + sizeof(SchedParams) + sizeof(BatchTables) + 2 * sizeof(void*) + 256 <= 4096,
+              "k_front's arguments and the 256 hidden bytes must fit the 4 KB kernel-argument segment");
+static_assert(FME_MAX_PICTURES <= kBlock && FME_MAX_LAMBDAS <= kBlock, "one lane per table entry");
+__global__ __launch_bounds__(kBlock) void k_front(BatchArgs a, WorkBufs w, SchedParams sp, BatchTables tab,
+                                                  PicDesc* __restrict__ d_pics, double* __restrict__ d_ml) {
   constexpr int kSeg = kFrontQ * (kBlock / 64);   // 64-job segments of the workgroup, in call order
   __shared__ FrontTables T;
   __shared__ int32_t seg[kSeg][kNumClasses + 1];  // jobs per class ([kNumClasses]: invalid), then their exclusive sums
@@ -350,7 +364,14 @@ __global__ __launch_bounds__(kBlock) void k_front(BatchArgs a, WorkBufs w, Sched
   const int base = blockIdx.x * kJobsPerScanBlock;
   fme_job jb[kFrontQ];
   front_load(a, w, base, jb);
-  front_tables(a, T);
+  front_tables(a, tab.pics, T);
+  if (blockIdx.x == 0) {
+    if (tid < FME_MAX_PICTURES) {
+      const BatchPic p = tab.pics[tid];
+      d_pics[tid] = PicDesc{p.luma, p.stride, p.width, p.height, nullptr, nullptr, 0, 0};
+    }
+    if (tid < FME_MAX_LAMBDAS) d_ml[tid] = tab.ml[tid];
+  }
   if (tid == 0) keyed = 0;
   for (int k = tid; k < kSeg * (kNumClasses + 1); k += kBlock) (&seg[0][0])[k] = 0;
   if (tid < 9) agg[tid] = -1;
@@ -731,8 +752,9 @@ void k_nn_tail(BatchArgs a, WorkBufs w, const float* __restrict__ nnp_g, int sta
 // ---------------------------------------------------------------------------------------
 static int nblocks(int n) { return (n + kJobsPerScanBlock - 1) / kJobsPerScanBlock; }
 
-hipError_t launch_front(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, hipStream_t s) {
-  hipLaunchKernelGGL(k_front, dim3(nblocks(a.n)), dim3(kBlock), 0, s, a, w, p);
+hipError_t launch_front(const BatchArgs& a, const WorkBufs& w, const SchedParams& p, const BatchTables& t,
+                        PicDesc* d_pics, double* d_ml, hipStream_t s) {
+  hipLaunchKernelGGL(k_front, dim3(nblocks(a.n)), dim3(kBlock), 0, s, a, w, p, t, d_pics, d_ml);
   return hipGetLastError();
 }
 
@@ -750,9 +772,9 @@ __global__ void k_put_state(uint32_t* dst, State12 st) {
   if (threadIdx.x < 12) dst[threadIdx.x] = st.v[threadIdx.x];
 }
 
-// The picture / lambda tables of a batch from a pinned, device-mapped host slot (fme_api.cpp
-// sync_tables: a ring of slots, each reused only once its launch has run), instead of a 3.5 KB
-// kernel argument at the edge of the argument segment.
+// The picture / lambda tables for everything but a refinement batch, from a pinned, device-mapped
+// host slot (fme_api.cpp sync_tables: a ring of slots, each reused only once its launch has run).
+// (A refinement batch carries them in k_front's argument instead, to save this launch.)
 __global__ __launch_bounds__(256) void k_put_tables(PicDesc* __restrict__ pics, double* __restrict__ ml,
                                                     const TablesSlot* __restrict__ t) {
   const int i = threadIdx.x;

@@ -158,7 +158,7 @@ class FrameReplay:
     def __init__(self, ctx, base_jobs, pool, lambda_of, n_steps, frames_per_step=1, world=1, rank=0, device=None,
                  group=None, defer_download=True, key_reqs=None, key_count=0, nn_rows=None,
                  download_engine="sdma", download_wgs=8, search_reserve=0, packed=True, copy_streams=1, slots=3,
-                 max_ahead=4, precreate_events=True, warm_engines=True, timeline=False, compute_streams=2):
+                 max_ahead=4, precreate_events=True, warm_engines=True, timeline=False, compute_streams=3):
         """ctx: an FmeContext on `device`; base_jobs: one frame's jobs (ref_id = reference
         distance - 1); pool: uint8 [P, H, W] host frames, frame g's pictures are pool[g % P];
         lambda_of(g): frame g's lambda (pool uint16: main10 samples for a bit-depth-10 context,
@@ -184,10 +184,14 @@ class FrameReplay:
         of 256 lanes) or "blit" (hipMemcpyAsync, which this ROCm runs as a blit kernel of hundreds of
         workgroups that take the search kernel's CUs).  search_reserve: resident search workgroups
         left free (fme_set_search_reserve), so the download kernel runs beside the search.
-        compute_streams: 2 (default) runs step k's batch on compute stream k % 2 (the device's
-        default stream and one more), so that the library lets consecutive batches overlap: step
+        compute_streams: 3 (default) runs step k's batch on compute stream k % 3 (the device's
+        default stream and two more), so that the library lets consecutive batches overlap: step
         k+1's front end and search do not wait for step k's NN tail, only the tails wait for each
-        other.  1 keeps every batch on the default stream, in series (kernel-alone profiling)."""
+        other, and step k+2's front end is not behind step k's tail in stream order either (it
+        waits for step k's search only).  2 alternates two streams: every second front end then
+        queues behind a tail that runs late.  1 keeps every batch on the default stream, in series
+        (kernel-alone profiling).  With the copy stream, three compute streams use the process's
+        four hardware queues."""
         import torch
         from .abi import JOB_PACKED_DTYPE
         from .runtime import FmeError, pack_jobs
@@ -244,8 +248,8 @@ class FrameReplay:
         self.org = torch.empty((n_steps * F, H, W), dtype=pdt, device=device)
         self.states = torch.zeros((n_steps, 12), dtype=torch.int32, device=device)
         self.s_comp = torch.cuda.default_stream(device)
-        if compute_streams not in (1, 2):
-            raise ValueError("compute_streams 1 or 2")
+        if compute_streams not in (1, 2, 3):
+            raise ValueError("compute_streams 1, 2 or 3")
         self.compute_streams = compute_streams
         # step k's batch runs on s_comps[k % compute_streams]
         self.s_comps = [self.s_comp] + [torch.cuda.Stream(device) for _ in range(compute_streams - 1)]
@@ -278,7 +282,13 @@ class FrameReplay:
         self.download_engine, self.download_wgs = download_engine, int(download_wgs)
         ctx.set_search_reserve(int(search_reserve))   # slots the search leaves to the download kernel
         ctx.set_search_event(None)                # set per step in issue()
-        self.pending = None                       # step whose download is not issued yet
+        self.pending = []                         # steps whose download is not issued yet, oldest first
+        # With three compute streams every tail runs as the next search drains (the next search is
+        # ready before the tail is, DESIGN.md section 5 "Hand-over"), so step k-1's batch ends only
+        # when step k's search does: its download, issued with step k, would sit at the head of the
+        # copy stream for a whole step and hold up the upload of step k+2 behind it.  The download
+        # of step k-2 is issued with step k instead (the result ring has a slot for it: slots >= 3).
+        self.download_lag = 2 if (compute_streams == 3 and R >= 3 and defer_download) else 1
         self.fixed_jobs = 0
         self.last_prefix = 0                      # longest carried-state prefix finish() re-ran
         self.r_out = {}
@@ -451,7 +461,7 @@ class FrameReplay:
             ctx.bind_picture_device(s, self.recon[f0 - REFS + s + REFS].data_ptr(), W, W, H)
 
     # -- one step -----------------------------------------------------------------------------
-    # Streams: step k's batch runs on compute stream k % 2 (the device's default stream and one more:
+    # Streams: step k's batch runs on compute stream k % 3 (the device's default stream and two more:
     # the library overlaps consecutive batches on different streams); every copy runs on one copy stream,
     # in series, as issue(k) queues them: the H2D of step k+1 (jobs, key bases, originals, the
     # published reconstruction; its slot was last read by step k+1-R), then the D2H of step k-1's
@@ -535,9 +545,9 @@ class FrameReplay:
         if not self.defer_download:
             self._download(k, self.ev_comp[k])
         else:
-            if self.pending is not None:   # step k's search started and step k-1's batch is over
-                self._download(self.pending, self.ev_search[k] if self.n > 0 else None)
-            self.pending = k
+            self.pending.append(k)
+            while len(self.pending) > self.download_lag:   # step k's search started and that step's batch is over
+                self._download(self.pending.pop(0), self.ev_search[k] if self.n > 0 else None)
         t.append(pc())
         self.host_ms.append((t[-1] - t[0]) * 1e3)
         self.host_seg.append([round((t[i + 1] - t[i]) * 1e3, 3) for i in range(len(t) - 1)])
@@ -570,9 +580,9 @@ class FrameReplay:
     def drain(self):
         """Issue the last step's download and wait for every stream; the library no longer records
         into this replay's search event afterwards (the context may outlive the replay)."""
-        if self.pending is not None:
-            self._download(self.pending, self.ev_comp[self.pending])
-            self.pending = None
+        while self.pending:
+            j = self.pending.pop(0)
+            self._download(j, self.ev_comp[j])
         self.s_copy.synchronize()
         for sc in self.s_comps:
             sc.synchronize()

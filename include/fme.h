@@ -346,11 +346,16 @@ int fme_set_search_event(fme_ctx* ctx, void* event);
 
 /* Overlapping consecutive batches.  The fme_refine*_device entry points may be called for batch
  * k+1 on another stream than batch k while batch k is still running: issue the batches on two
- * streams in turn.  The context then keeps two sets of work buffers (twice the memory: 192 bytes
- * per job of capacity) and orders the batches with stream waits on its own events: batch k+1's
+ * or, better, three streams in turn.  The context then keeps two sets of work buffers (twice the
+ * memory: 192 bytes per job of capacity, and 16 more for the four-entry ring of what a batch's
+ * tail still reads) and orders the batches with stream waits on its own events: batch k+1's
  * front end and search do not wait for batch k, only its NN tail waits for batch k's tail (the
- * carried NN_pred state), and batch k+2 waits for batch k's end.  Results are those of the same
- * calls on one stream, bit for bit.  fme_nn_set_state / fme_nn_reset_state between two such
+ * carried NN_pred state); batch k+2's front end waits for batch k's search and its search for
+ * batch k's end.  On two streams batch k+2 follows batch k in stream order, so its front end
+ * queues behind batch k's tail, which runs late whenever batch k+1's search has taken the chip
+ * first; on three streams (batch k on stream k % 3) it does not, and every search starts a few
+ * microseconds after the one before ends (DESIGN.md section 5 "Hand-over").  More than three
+ * streams buy nothing.  Results are those of the same calls on one stream, bit for bit.  fme_nn_set_state / fme_nn_reset_state between two such
  * calls take effect between the two tails.  A batch waits for every batch in flight first when
  * the key buffer was written since the last batch (fme_set_keys, fme_build_bipred_keys*), with
  * nn_mode 2, with FME_MAIN10_SEARCH=px, through the host-array entry points and the producers,
