@@ -16,6 +16,7 @@
 #include <memory>
 
 #include "fme_ctx.h"
+#include "fme_direct_host.h"
 
 using namespace fme;
 
@@ -180,6 +181,8 @@ int fme_destroy(fme_ctx* c) {
   c->d_surf_jobs.release(); c->d_surf_probe.release(); c->d_surf_out.release(); c->d_surf_pick.release();
   c->d_surf_invalid.release();
   for (auto& e : c->ev_surf)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->ev_direct)
     if (e) (void)hipEventDestroy(e);
   c->d_pics.release(); c->d_mlambda.release(); c->d_keys.release(); c->d_nn.release(); c->d_net.release();
   c->d_jobs.release(); c->d_res.release(); c->d_res1.release(); c->d_mv.release();
@@ -806,7 +809,154 @@ static int slot_records(fme_ctx* c, int n, fme_result** out) {
   return FME_OK;
 }
 
+// One NN-direct batch (include/fme_direct.h): front end -> EMI kernel -> NN tail -> evaluation
+// kernel, all enqueued without waiting for the device.
+// It takes a batch number like any other, so its slot, ring entry and counter block are nobody
+// else's and k_front leaves the block after next zeroed, but it is planned with kOvForeign: it
+// starts behind every batch in flight (batch_begin's waits are sync_tables' wait_batches), the
+// batch after it starts behind its end event, and the front end of the batch after that waits for
+// its end event too, so nothing overlaps it.  It writes the NN state, the work buffers and the
+// counter block like an ordinary batch and leaves the same bookkeeping: ev_done, last_slot /
+// last_ring (fme_refine_status), state_cur (fme_nn_get_state, fme_nn_copy_state_device),
+// batch_issued, keys_fresh, the noted stream.
+// The class kernel is the ordinary tail, launched as it is on the records the EMI kernel wrote,
+// whose frac_cost is a placeholder (0): what the tail derives from it (cost, bits) and its mv are
+// overwritten by the evaluation kernel, which follows in stream order, so no reader sees them: the
+// caller's records are complete only behind the evaluation kernel, and the compact form's tail
+// writes the context's internal records, never the caller's array.
+int fme::direct_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_result* d_mv, int n,
+                      hipStream_t s) {
+  if (c->cfg.nn_mode == 1 && !c->nn_loaded) return fail(FME_E_STATE, "fme_refine_direct: nn_mode set but no weights loaded");
+  if (c->cfg.nn_mode == 2 && !c->net_loaded) return fail(FME_E_STATE, "fme_refine_direct: nn_mode 2 but no net loaded");
+  if (c->cfg.nn_mode == 2 && c->nn_margin && n > c->nn_margin_cap)
+    return fail(FME_E_INVALID, "fme_refine_direct: %d jobs but the margin output holds %d", n, c->nn_margin_cap);
+  if (c->cfg.nn_mode == 2 && c->nn_logits && n > c->nn_logits_cap)
+    return fail(FME_E_INVALID, "fme_refine_direct: %d jobs but the logit output holds %d", n, c->nn_logits_cap);
+  bool grows = false;
+  FME_TRY(ensure_work(c, n, &grows));
+  const uint32_t features = kOvForeign | (c->keys_fresh ? kOvKeys : 0u) | (c->cfg.nn_mode == 2 ? kOvDeepNn : 0u) |
+                            (d_jobs == c->d_jobs.p ? kOvStaged : 0u) | (grows ? kOvGrow : 0u);
+  const OverlapPlan plan = overlap_plan(c->ov, s, features);   // serial
+  hipEvent_t search_end = nullptr, done = nullptr;
+  FME_TRY(enter_stream(c, s));
+  FME_TRY(batch_begin(c, plan, s, &search_end, &done));
+
+  // the tables travel in k_front's argument into the ring entry's copy, as in refine_batch
+  PicDesc* const d_pics = c->d_pics.p + (1 + plan.ring) * FME_MAX_PICTURES;
+  double* const d_ml = c->d_mlambda.p + (1 + plan.ring) * FME_MAX_LAMBDAS;
+  BatchTables tab;
+  for (int i = 0; i < FME_MAX_PICTURES; i++)
+    tab.pics[i] = BatchPic{c->pics[i].luma, c->pics[i].stride, c->pics[i].width, c->pics[i].height, 0};
+  std::memcpy(tab.ml, c->mlambda, sizeof(c->mlambda));
+  BatchArgs a = batch_args(c, d_jobs, n);
+  a.pics = d_pics;
+  a.mlambda = d_ml;
+  a.koff = c->koff[plan.ring].p;
+  a.res = d_res;
+  a.nn_mode = 1;
+  a.nn_in = c->nn_in;
+  a.nn_in_cap = c->nn_in_cap;
+  WorkBufs w = work_bufs(c, plan);   // mv_out null: the tail completes the full records
+  DirectArgs da{};
+  da.a = a;
+  da.sched = w.sched;
+  da.n = n;
+  da.bit_depth = c->cfg.bit_depth;
+
+  const bool prof = c->profiling;
+  hipEvent_t* ev = c->ev_direct;
+  if (prof) {
+    for (int k = 0; k < 5; k++)
+      if (!ev[k]) HIP_TRY(hipEventCreate(&ev[k]));
+    HIP_TRY(hipEventRecord(ev[0], s));
+  }
+  overlap_begin(c->ov);   // the counter blocks are in doubt until every launch is enqueued
+  HIP_TRY(launch_front(a, w, c->sched_p, tab, d_pics, d_ml, s));
+  if (prof) HIP_TRY(hipEventRecord(ev[1], s));
+  HIP_TRY(launch_direct_emi(da, s));
+  if (prof) HIP_TRY(hipEventRecord(ev[2], s));
+  HIP_TRY(hipEventRecord(search_end, s));
+  if (c->state_read_last) {   // a copy of the state the previous tail left comes first
+    if (c->state_read_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->state_read_last, 0));
+    c->state_read_last = nullptr;
+  }
+  FME_TRY(apply_pending_state(c, s));
+  HIP_TRY(c->cfg.nn_mode == 2
+              ? launch_nn_deep_tail(c->net, c->d_net.p, c->nn_margin, c->nn_logits, a, w, c->state_cur, c->nn_engine, s)
+              : launch_nn_tail(a, w, c->d_nn.p, c->state_cur, s));
+  if (prof) HIP_TRY(hipEventRecord(ev[3], s));
+  da.mv_out = d_mv;
+  HIP_TRY(launch_direct_eval(da, s));
+  if (prof) HIP_TRY(hipEventRecord(ev[4], s));
+  c->direct_timed = prof;
+  HIP_TRY(hipEventRecord(done, s));
+  c->ev_done = done;
+  c->last_slot = plan.slot;
+  c->last_ring = plan.ring;
+  c->keys_fresh = false;
+  overlap_commit(c->ov, s, features, plan);
+  c->batch_issued = true;
+  c->state_cur ^= 1;
+  return FME_OK;
+}
+
+// Host arrays, as refine_host: H2D of the jobs, the batch, D2H of the records and of the
+// rejected-job count, one synchronisation at the end.
+static int direct_host(fme_ctx* c, const fme_job* jobs, fme_result* res, int n, hipStream_t s) {
+  HIP_TRY(c->d_jobs.reserve(n));
+  HIP_TRY(c->d_res.reserve(n));
+  HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, (size_t)n * sizeof(fme_job), hipMemcpyHostToDevice, s));
+  FME_TRY(direct_batch(c, c->d_jobs.p, c->d_res.p, nullptr, n, s));
+  HIP_TRY(hipMemcpyAsync(res, c->d_res.p, (size_t)n * sizeof(fme_result), hipMemcpyDeviceToHost, s));
+  return check_rejected(c, s, "fme_refine_direct", "with an unsupported PU size or unset picture/lambda/key");
+}
+
+// The direct entry points' common start: the argument check (fme_direct_host.h); *run: enqueue.
+static int direct_enter(fme_ctx* c, const void* jobs, const void* out, int n, const char* name, bool* run) {
+  *run = false;
+  const int rq = direct_request(c, jobs, out, n, c ? c->cfg.nn_mode : 1);
+  if (rq == FME_E_STATE) return fail(rq, "%s: nn_mode 0 has no class to evaluate", name);
+  if (rq < 0) return fail(rq, "%s: bad argument (n = %d)", name, n);
+  if (rq == 0) {
+    HIP_TRY(hipSetDevice(c->device));
+    *run = true;
+  }
+  return FME_OK;
+}
+
 extern "C" {
+
+int fme_refine_direct(fme_ctx* c, const fme_job* jobs, fme_result* res, int n, void* stream) {
+  bool run;
+  FME_TRY(direct_enter(c, jobs, res, n, "fme_refine_direct", &run));
+  return run ? direct_host(c, jobs, res, n, static_cast<hipStream_t>(stream)) : FME_OK;
+}
+
+int fme_refine_direct_device(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, int n, void* stream) {
+  bool run;
+  FME_TRY(direct_enter(c, d_jobs, d_res, n, "fme_refine_direct_device", &run));
+  return run ? direct_batch(c, d_jobs, d_res, nullptr, n, static_cast<hipStream_t>(stream)) : FME_OK;
+}
+
+int fme_refine_direct_mv_device(fme_ctx* c, const fme_job* d_jobs, fme_mv_result* d_out, int n, void* stream) {
+  bool run;
+  FME_TRY(direct_enter(c, d_jobs, d_out, n, "fme_refine_direct_mv_device", &run));
+  if (!run) return FME_OK;
+  fme_result* d_res = nullptr;
+  FME_TRY(slot_records(c, n, &d_res));
+  return direct_batch(c, d_jobs, d_res, d_out, n, static_cast<hipStream_t>(stream));
+}
+
+int fme_refine_direct_last_ms(fme_ctx* c, float ms[4]) {
+  if (!c || !ms) return fail(FME_E_INVALID, "fme_refine_direct_last_ms: null argument");
+  if (!c->direct_timed) return fail(FME_E_STATE, "fme_refine_direct_last_ms: no profiled direct batch");
+  HIP_TRY(hipSetDevice(c->device));
+  hipEvent_t* e = c->ev_direct;
+  HIP_TRY(hipEventSynchronize(e[4]));
+  for (int k = 0; k < 3; k++) HIP_TRY(hipEventElapsedTime(&ms[k], e[1 + k], e[2 + k]));
+  HIP_TRY(hipEventElapsedTime(&ms[3], e[0], e[4]));
+  return FME_OK;
+}
 
 int fme_refine_device(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, int n, void* stream) {
   if (!c || (n > 0 && (!d_jobs || !d_res))) return fail(FME_E_INVALID, "fme_refine_device: null argument");

@@ -203,6 +203,10 @@ struct fme_ctx {
   hipStream_t surf_stream = nullptr;
   hipEvent_t ev_surf[2] = {nullptr, nullptr};
   bool surf_timed = false;
+  // NN-direct batches (include/fme_direct.h): timing events of the last one with profiling on: start,
+  // front end, EMI, class and evaluation kernel ends
+  hipEvent_t ev_direct[5] = {};
+  bool direct_timed = false;
   // integer search: staging for the host entry point, timing events
   fme::DevBuf<fme_tz_ext> d_tz_ext;
   fme::DevBuf<uint32_t> d_tz_sad;
@@ -313,6 +317,9 @@ int grow_keys(fme_ctx* c, size_t n);   // called before the key buffer is writte
 BatchArgs batch_args(const fme_ctx* c, const fme_job* jobs, int n);   // the fields every batch shares
 int refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_result* d_mv, int n, hipStream_t s,
                  const fme_job_packed* d_pjobs = nullptr, const int32_t* d_key_base = nullptr);
+// an NN-direct batch (include/fme_direct.h): the front end, the EMI kernel, the tail as the class
+// kernel, the evaluation kernel; planned like a batch that serialises (fme_overlap_host.h)
+int direct_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_result* d_mv, int n, hipStream_t s);
 int tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* d_sad, int n, void* stream, int16_t* d_emi,
            uint32_t* d_nn_in = nullptr, int ext_stride = (int)sizeof(fme_tz_ext));
 int check_rejected(fme_ctx* c, hipStream_t s, const char* name, const char* what);

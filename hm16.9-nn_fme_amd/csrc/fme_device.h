@@ -6,9 +6,11 @@
 #include <stdint.h>
 
 #include "../../include/fme.h"
+#include "../../include/fme_direct.h"
 #include "../../include/fme_merge.h"
 #include "../../include/fme_skip.h"
 #include "../../include/fme_surface.h"
+#include "fme_simd.h"
 #include "fme_srv_pack.h"
 
 namespace fme {
@@ -245,6 +247,23 @@ __device__ __forceinline__ int sched_perm_index(const Schedule* sc, int c0, int 
   for (; c < c1 - 1 && q >= sc->class_cnt[c]; c++) q -= sc->class_cnt[c];
   return sc->class_off[c] + q;
 }
+
+// The two kernels of an NN-direct batch (fme_direct.hip, include/fme_direct.h) beside k_front and
+// the tail: both walk the jobs in call order, 64 per workgroup, and do nothing in a batch k_front
+// rejected (sched->invalid) except, in the evaluation, marking the compact records.
+struct DirectArgs {
+  BatchArgs a;                // a.res: the batch's records (the caller's, or the context's for the compact form)
+  const Schedule* sched;      // of the batch's ring entry
+  fme_mv_result* mv_out;      // the evaluation's compact output (fme_refine_direct_mv_device), or null
+  int32_t n;
+  int32_t bit_depth;          // 8, or 10: uint16 planes
+};
+// per job the EMI square step of fme_refine (or the FME_JOB_NN_IN row, or nothing): mv_int, c, emi[],
+// n_emi into the record, every other field 0
+hipError_t launch_direct_emi(const DirectArgs& d, hipStream_t s);
+// per job the one sub-pel evaluation at the record's nn_class: mv, half / qtr, frac_cost, cost, bits
+// and FME_RES_NN_DIRECT into the record (or the compact record)
+hipError_t launch_direct_eval(const DirectArgs& d, hipStream_t s);
 
 // What the schedule needs to know about the search kernel: lanes per PU of each class (its unit
 // count rounded up to a power of two).
@@ -491,6 +510,21 @@ __device__ __forceinline__ int nn_pushes(const fme_job& j) {
   return (top ? cols : 0) + (left ? 1 : 0) + (right ? 1 : 0) + (bot ? cols : 0);
 }
 __device__ __forceinline__ bool nn_writes_c(const fme_job& j) { return (j.flags & (FME_JOB_EMI | FME_JOB_NN_IN)) != 0; }
+
+// xMotionEstimation's tail (TEncSearch.cpp:4586-4597) for job j's quarter-pel MV (fx, fy), whose
+// sub-pel cost is frac_cost: ruiBits = bits_in + the MV's bits, ruiCost = floor(fW (frac_cost -
+// getCost(mvBits))) + getCost(ruiBits), fW 0.5 for a bi-pred iteration; double like
+// TComRdCost::getCost, converted with gcc/x86-64's (Distortion)(double) semantics.  tail_job and the
+// NN-direct evaluation (fme_direct.hip) call it.  (k_nn_deep_tail keeps its own statement of the
+// same lines: through this function its load of frac_cost moves and its code changes.)
+__device__ __forceinline__ uint32_t me_tail(const fme_job& j, double ml, uint32_t frac_cost, int fx, int fy,
+                                            uint32_t& bits) {
+  const uint32_t mvb = simd::mv_bits(fx, fy, 0, j.mvp_x, j.mvp_y);
+  bits = (uint32_t)j.bits_in + mvb;
+  const double fw = (j.flags & FME_JOB_BIPRED) ? 0.5 : 1.0;
+  const double val = floor(fw * ((double)frac_cost - (double)simd::mv_cost(ml, mvb))) + (double)simd::mv_cost(ml, bits);
+  return (uint32_t)(int64_t)val;
+}
 
 // r: the job's record in call order (full-record output); src: its search record (the search
 // writes its fields into r itself, so src == r and only the tail's fields are written here).

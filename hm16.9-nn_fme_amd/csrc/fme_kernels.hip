@@ -690,12 +690,9 @@ __device__ __forceinline__ void tail_job(const BatchArgs& a, const WorkBufs& w, 
     offy = 2 * hy + qy;
   }
   const int fx = 4 * mvx + offx, fy = 4 * mvy + offy;
-  const uint32_t mvb = simd::mv_bits(fx, fy, 0, j.mvp_x, j.mvp_y);
-  const uint32_t bits = (uint32_t)j.bits_in + mvb;
-  const double fw = (j.flags & FME_JOB_BIPRED) ? 0.5 : 1.0;
-  const double val = floor(fw * ((double)frac_cost - (double)simd::mv_cost(ml, mvb))) + (double)simd::mv_cost(ml, bits);
-  // gcc/x86-64 (Distortion)(double) semantics for the cost
-  store_outputs(r, sr, w.mv_out, i, fx, fy, (uint32_t)(int64_t)val, bits, (uint8_t)cls, status);
+  uint32_t bits;
+  const uint32_t cost = me_tail(j, ml, frac_cost, fx, fy, bits);
+  store_outputs(r, sr, w.mv_out, i, fx, fy, cost, bits, (uint8_t)cls, status);
 }
 
 // One lane per job, one wave per workgroup, every wave on its own: the last-writer scan reads the

@@ -30,6 +30,7 @@
 #include "fme_mc_luma.h"
 #include "fme_simd.h"
 #include "fme_surface_host.h"
+#include "fme_unit_target.h"
 #include "fme_xlane.h"
 
 namespace fme {
@@ -47,7 +48,6 @@ typedef uint32_t sf_u4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t sf_u2 __attribute__((ext_vector_type(2), aligned(4)));
 typedef __attribute__((address_space(1))) sf_u4 g_sf_u4;
 typedef __attribute__((address_space(1))) sf_u2 g_sf_u2;
-typedef __attribute__((address_space(1))) const int16_t g_sf_i16;
 
 // Per-job state shared by the workgroup (LDS), filled by one thread per job.
 struct SfInfo {
@@ -199,44 +199,6 @@ __device__ __forceinline__ void sf_column(const int (&t)[12][4], const int (&o)[
   for (int fy = 0; fy < 4; fy++) sf_position<k10, 1>(t, fy, o, L, surf_index(dx, fy));
 }
 
-// o = the 4x4 block the unit at (x, y) is compared against: the job's key block or the original
-// (inside it: the job was validated)
-template <bool k10>
-__device__ __forceinline__ void sf_target(const SfInfo& in, int x, int y, bool valid, int (&o)[4][4]) {
-#pragma unroll
-  for (int r = 0; r < 4; r++)
-#pragma unroll
-    for (int c = 0; c < 4; c++) o[r][c] = 0;
-  if (!valid) return;
-  if (in.key) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      g_sf_i16* kp = (g_sf_i16*)(in.key + (size_t)(y - in.y + r) * in.w + (x - in.x));
-#pragma unroll
-      for (int c = 0; c < 4; c++) o[r][c] = (int)kp[c];
-    }
-    return;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    if constexpr (k10) {
-      const gu16c* op = (const gu16c*)(reinterpret_cast<const uint16_t*>(in.org) + (size_t)(y + r) * in.ostride + x);
-#pragma unroll
-      for (int c = 0; c < 4; c++) o[r][c] = (int)op[c];
-    } else {
-      const uint8_t* op = in.org + (size_t)(y + r) * in.ostride + x;
-      if (in.oal) {   // x is a multiple of 4
-        const uint32_t v = gld32(op);
-#pragma unroll
-        for (int c = 0; c < 4; c++) o[r][c] = (int)((v >> (8 * c)) & 255u);
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; c++) o[r][c] = (int)gld8(op + c);
-      }
-    }
-  }
-}
-
 template <bool k10>
 __global__ __launch_bounds__(kSfBlock) void k_cost_surface(SurfArgs a) {
   __shared__ SfInfo info[kSfTasks];
@@ -321,7 +283,7 @@ __global__ __launch_bounds__(kSfBlock) void k_cost_surface(SurfArgs a) {
       SfWin<k10> win;
       win.load(in, x + in.mvx, y + in.mvy, valid);
       int o[4][4];
-      sf_target<k10>(in, x, y, valid, o);
+      unit_target<k10>(in, x, y, valid, o);   // fme_unit_target.h
       SfLane L;
       L.row = out + q * kSfWords;
       L.G = G;

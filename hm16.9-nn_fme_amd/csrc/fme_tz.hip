@@ -22,6 +22,7 @@
 
 #include "fme_device.h"
 #include "fme_simd.h"
+#include "fme_tz_metric.h"
 
 // 1: a diagnostic build (make variant NAME=tzcount DEFS=-DFME_TZ_COUNT=1, tools/tz_counts.py) that
 // counts, per unit-shape kernel, the candidate windows read from the staged LDS tile and from global
@@ -36,6 +37,7 @@ __device__ unsigned long long g_tz_count[3][2];   // [kernel 4x8 / 8x4 / 8x8 uni
 #endif
 namespace {
 using namespace simd;
+using namespace tzm;   // unit_part, unit_part10: one unit's share of a candidate's distortion
 
 #define FME_AI __attribute__((always_inline))
 
@@ -275,43 +277,6 @@ __device__ __forceinline__ void load_window(uint32_t (&w)[UH][UW / 4 + 1], uint3
   }
 }
 
-// One unit's share of the distortion (TComRdCost metric of the integer search) for a window.
-template <int UW, int UH, int KW>
-__device__ __forceinline__ uint32_t unit_part(const uint32_t (&w)[UH][UW / 4 + 1], uint32_t s0,
-                                              const uint32_t (&kk)[UH][KW], int sk2, bool kbuf,
-                                              bool sad_metric, bool sub) {
-  int sop = 0, spp = 0;
-  uint32_t acc = 0;
-#pragma unroll
-  for (int r = 0; r < UH; r++) {
-    if (sub && (r & 1)) continue;
-#pragma unroll
-    for (int c = 0; c < UW / 4; c++) {
-      const uint32_t pv = __builtin_amdgcn_alignbyte(w[r][c + 1], w[r][c], s0);   // reference bytes
-      if (!kbuf) {
-        if (sad_metric) {
-          acc = __builtin_amdgcn_sad_u8(pv, kk[r][c], acc);
-        } else {
-          const uint32_t ps = pv ^ 0x80808080u;
-          sop = dot4(kk[r][c] ^ 0x80808080u, ps, sop);
-          spp = dot4(ps, ps, spp);
-        }
-      } else if constexpr (KW == UW / 2) {
-        const uint32_t d0 = pk_sub(kk[r][2 * c], lo_pair(pv));
-        const uint32_t d1 = pk_sub(kk[r][2 * c + 1], hi_pair(pv));
-        if (sad_metric) {
-          acc = udot2(pk_abs(d0), 0x00010001u, udot2(pk_abs(d1), 0x00010001u, acc));
-        } else {
-          acc = (uint32_t)dot2(d1, d1, dot2(d0, d0, (int)acc));
-        }
-      }
-    }
-  }
-  uint32_t part = (!kbuf && !sad_metric) ? (uint32_t)(sk2 - 2 * sop + spp) : acc;
-  if (sub) part <<= 1;
-  return part;
-}
-
 // ---- bit depth 10 (the main10 configurations, InternalBitDepth 10) --------------------------------
 // uint16 planes (strides in samples).  A unit's window row is UW / 2 + 1 dwords of sample pairs from
 // the even column at or left of the candidate; s0 = 1 when the candidate column is odd.
@@ -352,38 +317,6 @@ __device__ __forceinline__ void load_window10(uint32_t (&w)[UH][UW / 2 + 1], uin
       }
     }
   }
-}
-
-// One unit's share of the bit-depth-10 distortion: SSE sums (d * d) >> 4 per sample
-// (xGetSSE, TComRdCost.cpp:875-1130, DISTORTION_PRECISION_ADJUSTMENT(2 (bitDepth - 8))) as
-// (sum d^2 - sum (d^2 mod 16)) >> 4, with d^2 mod 16 = ((d & 7)^2) & 15; SAD returns the raw sum
-// (<< 1 with FEN subsampling), the block's >> 2 (xGetSAD12/24/48: uiSum >> (bitDepth - 8)) comes
-// after the group sum.  kk: the key as sample pairs (org samples, or the bi-pred int16 key).
-template <int UW, int UH>
-__device__ __forceinline__ uint32_t unit_part10(const uint32_t (&w)[UH][UW / 2 + 1], uint32_t s0,
-                                                const uint32_t (&kk)[UH][UW / 2], bool sad_metric, bool sub) {
-  int sq = 0;
-  uint32_t lo = 0, acc = 0;
-#pragma unroll
-  for (int r = 0; r < UH; r++) {
-    if (sub && (r & 1)) continue;
-#pragma unroll
-    for (int c = 0; c < UW / 2; c++) {
-      const uint32_t pv = s0 ? __builtin_amdgcn_alignbyte(w[r][c + 1], w[r][c], 2u) : w[r][c];
-      const uint32_t dd = pk_sub(kk[r][c], pv);
-      if (sad_metric) {
-        acc = udot2(pk_abs(dd), 0x00010001u, acc);
-      } else {
-        sq = dot2(dd, dd, sq);
-        // d^2 mod 16 by d & 7 (0 1 4 9 0 9 4 1) from a byte table: one v_and_or makes the v_perm
-        // selector (byte 0x0C selects zero), the perm gives the pair of residues as u16 halves
-        const uint32_t sel = (dd & 0x00070007u) | 0x0C000C00u;
-        lo = udot2(__builtin_amdgcn_perm(0x01040900u, 0x09040100u, sel), 0x00010001u, lo);
-      }
-    }
-  }
-  if (sad_metric) return sub ? acc << 1 : acc;
-  return ((uint32_t)sq - lo) >> 4;
 }
 
 // ---- wave-uniform search: one wave per PU ------------------------------------------------------

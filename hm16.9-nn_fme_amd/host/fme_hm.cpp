@@ -71,6 +71,8 @@ std::vector<float> loadWeights(const std::string& dir_in, int qp) {
 // ---- FracSearch --------------------------------------------------------------------------
 
 FracSearch::FracSearch(const SearchConfig& cfg) : cfg_(cfg) {
+  if (cfg.nnDirect && cfg.nnMode == 0)
+    throw Error(FME_E_STATE, "SearchConfig::nnDirect needs nnMode != 0: there is no class to evaluate");
   fme_config c{};
   c.bit_depth = cfg.bitDepth;
   c.use_hadamard = cfg.useHadamardME ? 1 : 0;
@@ -87,6 +89,12 @@ FracSearch::FracSearch(const SearchConfig& cfg) : cfg_(cfg) {
 
 FracSearch::~FracSearch() {
   if (ctx_) fme_destroy(ctx_);
+}
+
+void FracSearch::refine(const fme_job* jobs, fme_result* results, int n) {
+  std::lock_guard<std::mutex> lock(mu_);
+  check(cfg_.nnDirect ? fme_refine_direct(ctx_, jobs, results, n, nullptr) : fme_refine(ctx_, jobs, results, n, nullptr),
+        cfg_.nnDirect ? "fme_refine_direct" : "fme_refine");
 }
 
 void FracSearch::setLambda(double lambda) { mlambda_ = 65536.0 * std::sqrt(lambda); }  // TComRdCost.cpp:104-117
@@ -441,8 +449,9 @@ void CtuRowBatcher::worker() {
       fme_ctx* c = search_.ctx();
       int rc = FME_OK;
       if (!r->keys.empty()) rc = fme_set_keys(c, r->keys.data(), r->keys.size(), nullptr);
-      if (rc == FME_OK && !r->jobs.empty())
-        rc = fme_refine(c, r->jobs.data(), r->results.data(), (int)r->jobs.size(), nullptr);
+      if (rc == FME_OK && !r->jobs.empty())   // (FracSearch::refine's call, under the lock already held)
+        rc = search_.nnDirect() ? fme_refine_direct(c, r->jobs.data(), r->results.data(), (int)r->jobs.size(), nullptr)
+                                : fme_refine(c, r->jobs.data(), r->results.data(), (int)r->jobs.size(), nullptr);
       if (rc != FME_OK) {
         r->rc = rc;
         r->err = fme_last_error();

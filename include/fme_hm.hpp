@@ -12,6 +12,7 @@
 //     NN_pred + tail, TEncSearch.cpp:4529-4597, 5037-5050) of one CTU row, hands the row to a
 //     worker thread that runs it on the GPU while the caller fills the next row, and returns
 //     the results in queue order (the NN's carried state follows queue order across rows).
+//     With SearchConfig::nnDirect the rows run NN-direct (include/fme_direct.h) instead.
 //
 // Pel planes are HM's int16 samples; pictures are converted to the library's planes at the
 // search's bit depth (SearchConfig::bitDepth): uint8_t samples at 8 bits, uint16_t at 10 (the
@@ -33,6 +34,7 @@
 #include <vector>
 
 #include "fme.h"
+#include "fme_direct.h"
 #include "fme_merge.h"
 #include "fme_skip.h"
 #include "fme_surface.h"
@@ -68,6 +70,11 @@ struct SearchConfig {
   std::string weightsDir;     // holds nn2_qp{22,27,32,37}.bin (empty: $FME_WEIGHTS_DIR or the
                               // package's weights/ directory next to libfme_amd.so)
   int bitDepth = 8;           // InternalBitDepth: 8 or 10 (anything else: Error, FME_E_UNSUPPORTED)
+  bool nnDirect = false;      // the batch path runs fme_refine_direct (include/fme_direct.h): the EMI step,
+                              // NN_pred() and one evaluation at its position instead of FracDIF; frac_cost /
+                              // cost are then the returned MV's own, which the shipped encoder never
+                              // computes.  Needs nnMode != 0 (else Error, FME_E_STATE).  The single calls
+                              // (xPatternSearchFracDIF, NN_pred) are as they were.
 };
 
 // Reads weights/nn2_qp<set>.bin (2060 float64 -> float32, the set TEncSearch::init picks).
@@ -107,7 +114,12 @@ class FracSearch {
   void setPicture16(int id, const uint16_t* plane, int stride, int width, int height);
   void setLambdaSlot(int lambdaId, double lambda);
 
+  // The batch path: n sub-pel jobs in call order, synchronous, under mutex(): fme_refine, or with
+  // SearchConfig::nnDirect fme_refine_direct.  CtuRowBatcher's rows run through it.
+  void refine(const fme_job* jobs, fme_result* results, int n);
+
   int bitDepth() const { return cfg_.bitDepth; }
+  bool nnDirect() const { return cfg_.nnDirect; }
   fme_ctx* ctx() const { return ctx_; }
   std::mutex& mutex() { return mu_; }   // serialises context use with a running batcher
 
