@@ -17,6 +17,7 @@
 
 #include "fme_ctx.h"
 #include "fme_direct_host.h"
+#include "fme_extern_host.h"
 
 using namespace fme;
 
@@ -183,6 +184,9 @@ int fme_destroy(fme_ctx* c) {
   for (auto& e : c->ev_surf)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->ev_direct)
+    if (e) (void)hipEventDestroy(e);
+  c->d_ext_rows.release(); c->d_ext_cls.release(); c->d_ext_refused.release();
+  for (auto& e : c->ev_extern)
     if (e) (void)hipEventDestroy(e);
   c->d_pics.release(); c->d_mlambda.release(); c->d_keys.release(); c->d_nn.release(); c->d_net.release();
   c->d_jobs.release(); c->d_res.release(); c->d_res1.release(); c->d_mv.release();
@@ -924,7 +928,233 @@ static int direct_enter(fme_ctx* c, const void* jobs, const void* out, int n, co
   return FME_OK;
 }
 
+// ---- the external predictor (include/fme_extern.h) -----------------------------------------------
+// Both batches below are a direct batch cut at the class, and are planned and booked like one
+// (direct_batch above): a batch number of their own, kOvForeign, so they start behind every batch in
+// flight and nothing overlaps them; ev_done, last_slot / last_ring, batch_issued, keys_fresh and the
+// noted stream are left as by any batch.
+
+// What the two share: the plan, the waits, the tables, k_front.
+struct ExternBatch {
+  OverlapPlan plan;
+  uint32_t features;
+  hipEvent_t search_end, done;
+  BatchArgs a;
+  WorkBufs w;
+};
+// zero (may be null): a counter zeroed behind the batch's waits, before its first launch.
+static int extern_begin(fme_ctx* c, const fme_job* d_jobs, fme_result* d_rec, int n, hipStream_t s, int32_t* zero,
+                        ExternBatch* b) {
+  bool grows = false;
+  FME_TRY(ensure_work(c, n, &grows));
+  b->features = kOvForeign | (c->keys_fresh ? kOvKeys : 0u) | (d_jobs == c->d_jobs.p ? kOvStaged : 0u) |
+                (grows ? kOvGrow : 0u);
+  b->plan = overlap_plan(c->ov, s, b->features);   // serial
+  b->search_end = b->done = nullptr;
+  FME_TRY(enter_stream(c, s));
+  FME_TRY(batch_begin(c, b->plan, s, &b->search_end, &b->done));
+  if (zero) HIP_TRY(hipMemsetAsync(zero, 0, sizeof(int32_t), s));   // (its last user, an earlier batch, is over)
+  PicDesc* const d_pics = c->d_pics.p + (1 + b->plan.ring) * FME_MAX_PICTURES;
+  double* const d_ml = c->d_mlambda.p + (1 + b->plan.ring) * FME_MAX_LAMBDAS;
+  BatchTables tab;
+  for (int i = 0; i < FME_MAX_PICTURES; i++)
+    tab.pics[i] = BatchPic{c->pics[i].luma, c->pics[i].stride, c->pics[i].width, c->pics[i].height, 0};
+  std::memcpy(tab.ml, c->mlambda, sizeof(c->mlambda));
+  b->a = batch_args(c, d_jobs, n);
+  b->a.pics = d_pics;
+  b->a.mlambda = d_ml;
+  b->a.koff = c->koff[b->plan.ring].p;
+  b->a.res = d_rec;
+  b->a.nn_mode = 1;
+  b->a.nn_in = nullptr;   // (none bound: the entry points refuse otherwise)
+  b->a.nn_in_cap = 0;
+  b->w = work_bufs(c, b->plan);
+  const bool prof = c->profiling;
+  if (prof) {
+    for (auto& e : c->ev_extern)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(c->ev_extern[0], s));
+  }
+  c->extern_timed = false;
+  overlap_begin(c->ov);   // the counter blocks are in doubt until every launch is enqueued
+  HIP_TRY(launch_front(b->a, b->w, c->sched_p, tab, d_pics, d_ml, s));
+  if (prof) HIP_TRY(hipEventRecord(c->ev_extern[1], s));
+  return FME_OK;
+}
+static int extern_end(fme_ctx* c, hipStream_t s, const ExternBatch& b, unsigned phases) {
+  c->extern_phases = phases;
+  c->extern_timed = c->profiling;
+  HIP_TRY(hipEventRecord(b.done, s));
+  c->ev_done = b.done;
+  c->last_slot = b.plan.slot;
+  c->last_ring = b.plan.ring;
+  c->keys_fresh = false;
+  overlap_commit(c->ov, s, b.features, b.plan);
+  c->batch_issued = true;
+  return FME_OK;
+}
+static DirectArgs extern_direct_args(const fme_ctx* c, const ExternBatch& b, int n) {
+  DirectArgs da{};
+  da.a = b.a;
+  da.sched = b.w.sched;
+  da.n = n;
+  da.bit_depth = c->cfg.bit_depth;
+  return da;
+}
+
+// One inputs batch: front end -> EMI kernel (on d_rec, context-internal records) -> rows kernel.  It
+// hands the NN state on like a tail, in every nn_mode: it waits for a copy of the state in flight,
+// applies a pending set / reset, writes the other state slot and flips state_cur.
+static int inputs_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_rec, fme_nn_row* d_rows, int n, hipStream_t s) {
+  ExternBatch b;
+  FME_TRY(extern_begin(c, d_jobs, d_rec, n, s, nullptr, &b));
+  const bool prof = c->profiling;
+  HIP_TRY(launch_direct_emi(extern_direct_args(c, b, n), s));
+  if (prof) HIP_TRY(hipEventRecord(c->ev_extern[2], s));
+  HIP_TRY(hipEventRecord(b.search_end, s));
+  if (c->state_read_last) {   // a copy of the state the previous tail left comes first
+    if (c->state_read_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->state_read_last, 0));
+    c->state_read_last = nullptr;
+  }
+  FME_TRY(apply_pending_state(c, s));
+  const bool slot_reset = c->cfg.nn_mode == 2 && c->net_loaded && (c->net.input_flags & FME_NN_IN_SLOT_RESET);
+  HIP_TRY(launch_nn_rows(b.a, b.w, d_rows, c->state_cur, slot_reset, s));
+  if (prof) HIP_TRY(hipEventRecord(c->ev_extern[3], s));
+  FME_TRY(extern_end(c, s, b, 3u));
+  c->state_cur ^= 1;
+  return FME_OK;
+}
+
+// One evaluation batch: front end -> EMI kernel unless the caller brought rows -> evaluation at the
+// caller's classes.  d_res: the full records (with d_mv and no rows: context-internal ones the EMI
+// kernel writes; with d_mv and rows: null).  The NN state is not touched.
+static int at_batch(fme_ctx* c, const fme_job* d_jobs, const fme_nn_row* d_rows, const uint8_t* d_cls,
+                    fme_result* d_res, fme_mv_result* d_mv, int n, hipStream_t s) {
+  HIP_TRY(c->d_ext_refused.reserve(1));
+  ExternBatch b;
+  FME_TRY(extern_begin(c, d_jobs, d_res, n, s, c->d_ext_refused.p, &b));
+  const bool prof = c->profiling;
+  ExternArgs x{};
+  x.d = extern_direct_args(c, b, n);
+  if (!d_rows) {
+    HIP_TRY(launch_direct_emi(x.d, s));
+    if (prof) HIP_TRY(hipEventRecord(c->ev_extern[2], s));
+  }
+  HIP_TRY(hipEventRecord(b.search_end, s));
+  x.d.mv_out = d_mv;
+  x.at = AtArgs{d_rows, d_cls, c->d_ext_refused.p};
+  x.n = n;
+  x.bit_depth = c->cfg.bit_depth;
+  HIP_TRY(launch_at_eval(x, s));
+  if (prof) HIP_TRY(hipEventRecord(c->ev_extern[4], s));
+  FME_TRY(extern_end(c, s, b, d_rows ? 4u : 5u));
+  c->ev_at_done = b.done;
+  return FME_OK;
+}
+
+// The families' common start: the argument check (fme_extern_host.h); *run: enqueue.
+static int extern_enter(fme_ctx* c, int rq, int n, const char* name, bool* run) {
+  *run = false;
+  if (rq == FME_E_STATE) return fail(rq, "%s: NN input rows are bound (fme_set_nn_inputs): the inputs are the caller's", name);
+  if (rq < 0) return fail(rq, "%s: bad argument (n = %d)", name, n);
+  if (rq == 0) {
+    HIP_TRY(hipSetDevice(c->device));
+    *run = true;
+  }
+  return FME_OK;
+}
+
 extern "C" {
+
+int fme_nn_inputs(fme_ctx* c, const fme_job* jobs, fme_nn_row* rows, int n, void* stream) {
+  bool run;
+  FME_TRY(extern_enter(c, extern_inputs_request(c, jobs, rows, n, c && c->nn_in), n, "fme_nn_inputs", &run));
+  if (!run) return FME_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(c->d_jobs.reserve(n));
+  HIP_TRY(c->d_res.reserve(n));
+  HIP_TRY(c->d_ext_rows.reserve(n));
+  HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, (size_t)n * sizeof(fme_job), hipMemcpyHostToDevice, s));
+  FME_TRY(inputs_batch(c, c->d_jobs.p, c->d_res.p, c->d_ext_rows.p, n, s));
+  HIP_TRY(hipMemcpyAsync(rows, c->d_ext_rows.p, (size_t)n * sizeof(fme_nn_row), hipMemcpyDeviceToHost, s));
+  return check_rejected(c, s, "fme_nn_inputs", "with an unsupported PU size or unset picture/lambda/key");
+}
+
+int fme_nn_inputs_device(fme_ctx* c, const fme_job* d_jobs, fme_nn_row* d_rows, int n, void* stream) {
+  bool run;
+  FME_TRY(extern_enter(c, extern_inputs_request(c, d_jobs, d_rows, n, c && c->nn_in), n, "fme_nn_inputs_device", &run));
+  if (!run) return FME_OK;
+  fme_result* d_rec = nullptr;
+  FME_TRY(slot_records(c, n, &d_rec));
+  return inputs_batch(c, d_jobs, d_rec, d_rows, n, static_cast<hipStream_t>(stream));
+}
+
+int fme_refine_at(fme_ctx* c, const fme_job* jobs, const fme_nn_row* rows, const uint8_t* cls, fme_result* res, int n,
+                  void* stream) {
+  bool run;
+  FME_TRY(extern_enter(c, extern_at_request(c, jobs, cls, res, n, c && c->nn_in), n, "fme_refine_at", &run));
+  if (!run) return FME_OK;
+  const int bad = extern_first_refused(jobs, rows, cls, n);
+  if (bad >= 0)
+    return fail(FME_E_INVALID, "fme_refine_at: job %d has class %d%s", bad, (int)cls[bad],
+                extern_class_ok(cls[bad]) ? " and a row that is not its own" : " (0..48)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(c->d_jobs.reserve(n));
+  HIP_TRY(c->d_res.reserve(n));
+  HIP_TRY(c->d_ext_cls.reserve(n));
+  if (rows) HIP_TRY(c->d_ext_rows.reserve(n));
+  HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, (size_t)n * sizeof(fme_job), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_ext_cls.p, cls, (size_t)n, hipMemcpyHostToDevice, s));
+  if (rows) HIP_TRY(hipMemcpyAsync(c->d_ext_rows.p, rows, (size_t)n * sizeof(fme_nn_row), hipMemcpyHostToDevice, s));
+  FME_TRY(at_batch(c, c->d_jobs.p, rows ? c->d_ext_rows.p : nullptr, c->d_ext_cls.p, c->d_res.p, nullptr, n, s));
+  // the rejected-job count first: an invalid batch leaves the caller's array as it was
+  FME_TRY(check_rejected(c, s, "fme_refine_at", "with an unsupported PU size or unset picture/lambda/key"));
+  HIP_TRY(hipMemcpy(res, c->d_res.p, (size_t)n * sizeof(fme_result), hipMemcpyDeviceToHost));
+  return FME_OK;
+}
+
+int fme_refine_at_device(fme_ctx* c, const fme_job* d_jobs, const fme_nn_row* d_rows, const uint8_t* d_cls,
+                         fme_result* d_res, int n, void* stream) {
+  bool run;
+  FME_TRY(extern_enter(c, extern_at_request(c, d_jobs, d_cls, d_res, n, c && c->nn_in), n, "fme_refine_at_device", &run));
+  return run ? at_batch(c, d_jobs, d_rows, d_cls, d_res, nullptr, n, static_cast<hipStream_t>(stream)) : FME_OK;
+}
+
+int fme_refine_at_mv_device(fme_ctx* c, const fme_job* d_jobs, const fme_nn_row* d_rows, const uint8_t* d_cls,
+                            fme_mv_result* d_out, int n, void* stream) {
+  bool run;
+  FME_TRY(extern_enter(c, extern_at_request(c, d_jobs, d_cls, d_out, n, c && c->nn_in), n, "fme_refine_at_mv_device", &run));
+  if (!run) return FME_OK;
+  fme_result* d_rec = nullptr;   // the EMI kernel's records; with rows nothing reads or writes them
+  if (!d_rows) FME_TRY(slot_records(c, n, &d_rec));
+  return at_batch(c, d_jobs, d_rows, d_cls, d_rec, d_out, n, static_cast<hipStream_t>(stream));
+}
+
+int fme_refine_at_status(fme_ctx* c) {
+  if (!c) return fail(FME_E_INVALID, "fme_refine_at_status: null ctx");
+  if (!c->ev_at_done) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->ev_at_done));
+  int32_t v = 0;
+  HIP_TRY(hipMemcpy(&v, c->d_ext_refused.p, sizeof(v), hipMemcpyDeviceToHost));
+  return v;
+}
+
+int fme_extern_last_ms(fme_ctx* c, float ms[4]) {
+  if (!c || !ms) return fail(FME_E_INVALID, "fme_extern_last_ms: null argument");
+  if (!c->extern_timed) return fail(FME_E_STATE, "fme_extern_last_ms: no profiled batch of fme_nn_inputs* / fme_refine_at*");
+  HIP_TRY(hipSetDevice(c->device));
+  hipEvent_t* e = c->ev_extern;
+  const unsigned ph = c->extern_phases;
+  const int last = (ph & 4u) ? 4 : 3;
+  HIP_TRY(hipEventSynchronize(e[last]));
+  ms[0] = ms[1] = ms[2] = 0.f;
+  if (ph & 1u) HIP_TRY(hipEventElapsedTime(&ms[0], e[1], e[2]));
+  if (ph & 2u) HIP_TRY(hipEventElapsedTime(&ms[1], e[2], e[3]));
+  if (ph & 4u) HIP_TRY(hipEventElapsedTime(&ms[2], e[(ph & 1u) ? 2 : 1], e[4]));
+  HIP_TRY(hipEventElapsedTime(&ms[3], e[0], e[last]));
+  return FME_OK;
+}
 
 int fme_refine_direct(fme_ctx* c, const fme_job* jobs, fme_result* res, int n, void* stream) {
   bool run;

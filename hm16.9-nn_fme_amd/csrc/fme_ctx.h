@@ -207,6 +207,17 @@ struct fme_ctx {
   // front end, EMI, class and evaluation kernel ends
   hipEvent_t ev_direct[5] = {};
   bool direct_timed = false;
+  // the external predictor (include/fme_extern.h): staging of the host forms' rows and classes, the
+  // count of the jobs the last fme_refine_at* batch refused one by one and that batch's end event (one
+  // of done_ev), and the timing events of the last call of either family with profiling on: start,
+  // front end, EMI, rows and evaluation kernel ends (extern_phases: bit 0 EMI, 1 rows, 2 evaluation ran)
+  fme::DevBuf<fme_nn_row> d_ext_rows;
+  fme::DevBuf<uint8_t> d_ext_cls;
+  fme::DevBuf<int32_t> d_ext_refused;
+  hipEvent_t ev_at_done = nullptr;
+  hipEvent_t ev_extern[5] = {};
+  unsigned extern_phases = 0;
+  bool extern_timed = false;
   // integer search: staging for the host entry point, timing events
   fme::DevBuf<fme_tz_ext> d_tz_ext;
   fme::DevBuf<uint32_t> d_tz_sad;

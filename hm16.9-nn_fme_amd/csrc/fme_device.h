@@ -7,6 +7,7 @@
 
 #include "../../include/fme.h"
 #include "../../include/fme_direct.h"
+#include "../../include/fme_extern.h"
 #include "../../include/fme_merge.h"
 #include "../../include/fme_skip.h"
 #include "../../include/fme_surface.h"
@@ -264,6 +265,28 @@ hipError_t launch_direct_emi(const DirectArgs& d, hipStream_t s);
 // per job the one sub-pel evaluation at the record's nn_class: mv, half / qtr, frac_cost, cost, bits
 // and FME_RES_NN_DIRECT into the record (or the compact record)
 hipError_t launch_direct_eval(const DirectArgs& d, hipStream_t s);
+
+// The external predictor's two kernels (fme_extern.hip, include/fme_extern.h).
+// What the evaluation reads beside a direct batch's arguments:
+struct AtArgs {
+  const fme_nn_row* rows;     // the jobs' NN input rows, or null: the EMI kernel wrote the records
+  const uint8_t* cls;         // one class per job
+  int32_t* refused;           // count of the jobs refused one by one (zeroed before the launch)
+};
+struct ExternArgs {
+  DirectArgs d;               // d.a.res: the records (null with rows and the compact output)
+  AtArgs at;
+  int32_t n;
+  int32_t bit_depth;
+};
+// per job the one sub-pel evaluation at at.cls[i]; the record's EMI fields from the row, or left as
+// the EMI kernel wrote them
+hipError_t launch_at_eval(const ExternArgs& x, hipStream_t s);
+// the tail without the net: per job the NN inputs it resolves (a.res: the records the EMI kernel
+// wrote) into rows[i], and the carried state from slot state_in to the other one, in every nn_mode;
+// slot_reset: the loaded net's FME_NN_IN_SLOT_RESET rule
+hipError_t launch_nn_rows(const BatchArgs& a, const WorkBufs& w, fme_nn_row* rows, int state_in, bool slot_reset,
+                          hipStream_t s);
 
 // What the schedule needs to know about the search kernel: lanes per PU of each class (its unit
 // count rounded up to a power of two).

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fme_device.h"
+#include "fme_direct_eval.h"
 #include "fme_direct_host.h"
 #include "fme_mc_luma.h"
 #include "fme_simd.h"
@@ -38,61 +39,7 @@
 namespace fme {
 namespace {
 
-using namespace simd;
-using namespace mcl;
-using namespace xlane;
-
-constexpr int kDiBlock = 256;
-constexpr int kDiTasks = kGroupTasks;   // consecutive jobs per workgroup, set up by its first wave
-
-typedef uint32_t di_u4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t di_u2 __attribute__((ext_vector_type(2), aligned(4)));
-typedef __attribute__((address_space(1))) di_u4 g_di_u4;
-typedef __attribute__((address_space(1))) di_u2 g_di_u2;
-typedef __attribute__((address_space(1))) uint32_t g_di_u32;
-typedef __attribute__((address_space(1))) const di_u4 g_di_cu4;
-
-// Per-job state shared by the workgroup (LDS), filled by one thread per job.
-struct DiInfo {
-  const uint8_t* ref;
-  const uint8_t* org;
-  const int16_t* key;         // the job's key block (rows of w), or null: the original at (x, y)
-  int rstride, ral;           // reference stride, dword-aligned rows
-  int ostride, oal;
-  int pw, ph;                 // the reference picture's size
-  int x, y, w, uxn, units;    // units 0: the job has no work in this kernel
-  int lanes, start;           // lane group size (0: no work) and first lane slot
-  int mode;                   // EMI: bit 0 the SAD metric, bit 1 FEN row subsampling; evaluation: kDist*
-  int bx, by;                 // added to a unit's origin: the integer MV (evaluation: + the offset's integer part)
-  int fx, fy;                 // evaluation: the quarter-pel fractions
-};
-
-// What both kernels' first wave does per job: the pictures, the target and the unit counts.
-__device__ __forceinline__ void di_fill(const BatchArgs& a, const fme_job& j, DiInfo& in) {
-  const PicDesc p = a.pics[j.ref_id];
-  in.ref = p.luma;
-  in.rstride = p.stride;
-  in.ral = dword_rows(p.luma, p.stride);
-  in.pw = p.width;
-  in.ph = p.height;
-  in.key = nullptr;
-  in.org = nullptr;
-  in.ostride = 0;
-  in.oal = 0;
-  if (j.key_offset >= 0) {
-    in.key = a.keys + j.key_offset;
-  } else {
-    const PicDesc o = a.pics[j.org_id];
-    in.org = o.luma;
-    in.ostride = o.stride;
-    in.oal = dword_rows(o.luma, o.stride) && (j.x & 3) == 0;
-  }
-  in.x = j.x;
-  in.y = j.y;
-  in.w = j.w;
-  in.uxn = j.w >> 2;
-  in.units = (j.w >> 2) * (j.h >> 2);
-}
+using namespace di;   // the lanes' per-job state and the evaluation (fme_direct_eval.h)
 
 // ---- the EMI step's unit: the 6x6 window at rows and columns -1..4 and the nine positions ---------
 // 8 bits: window rows of three dwords from the aligned column at or left of column -1 (s0: the byte
@@ -321,106 +268,6 @@ __global__ __launch_bounds__(kDiBlock) void k_direct_emi(DirectArgs d) {
   out[3] = di_u4{emi[5], emi[6], emi[7], (uint32_t)n_emi};
 }
 
-template <bool k10>
-__global__ __launch_bounds__(kDiBlock) void k_direct_eval(DirectArgs d) {
-  const BatchArgs& a = d.a;
-  const int t = (int)threadIdx.x, lane = t & 63;
-  const int t0 = (int)blockIdx.x * kDiTasks;
-  const int nt = min(kDiTasks, d.n - t0);   // jobs of this workgroup (> 0 by the grid)
-  if (d.sched->invalid) {   // a rejected batch: the tail marked the full records; the compact ones here
-    if (d.mv_out && t < nt) d.mv_out[t0 + t].status = FME_RES_REJECTED;
-    return;
-  }
-  __shared__ DiInfo info[kDiTasks];
-  __shared__ uint32_t dist[kDiTasks];
-  __shared__ uint8_t slot_task[kGroupSlots];
-  __shared__ int total_lanes;
-  fme_job j{};   // first wave: lane t keeps job t0 + t, its integer MV, class and the record's last word
-  int mvx = 0, mvy = 0, cls = 24;
-  uint32_t last = 0;
-  if (t < kDiTasks) {
-    DiInfo& in = info[t];
-    int lanes = 0;
-    dist[t] = 0u;
-    in.units = 0;
-    in.uxn = 1;
-    in.mode = kDistSad;
-    if (t < nt) {
-      j = load_job(a, t0 + t);
-      const g_di_u32* rec = (const g_di_u32*)(a.res + t0 + t);
-      const uint32_t mvw = rec[0];
-      last = rec[15];   // n_emi, nn_class, status
-      mvx = (int16_t)(mvw & 0xFFFFu);
-      mvy = (int16_t)(mvw >> 16);
-      cls = min((int)((last >> 8) & 0xFFu), kDirectClasses - 1);   // (a class always: nn_mode 0 is refused)
-      di_fill(a, j, in);
-      const int ox = direct_dx(cls), oy = direct_dy(cls);
-      in.bx = mvx + direct_int(ox);
-      in.by = mvy + direct_int(oy);
-      in.fx = direct_frac(ox);
-      in.fy = direct_frac(oy);
-      in.mode = dist_mode(a.use_hadamard && !(j.flags & FME_JOB_LOSSLESS), j.w, j.h);
-      lanes = group_lanes(in.units);
-    }
-    in.lanes = lanes;
-    in.start = pack_groups(lanes, lane, slot_task, total_lanes);
-  }
-  __syncthreads();
-  const int total = total_lanes;
-  for (int g0 = 0; g0 < total; g0 += kDiBlock) {   // workgroup-uniform
-    const int g = g0 + t;
-    const bool act = g < total;
-    const int q = act ? (int)slot_task[g >> 2] : 0;
-    const DiInfo& in = info[q];
-    const int G = act ? in.lanes : 64;
-    const int li = g - in.start;
-    const int units = act ? in.units : 0;
-    for (int u = li; __any(u < units); u += G) {   // wave-uniform
-      const bool valid = u < units;
-      const int mode = in.mode, uxn = max(in.uxn, 1);
-      int ux, uy;
-      unit_xy(u, uxn, mode == kDistHad8, ux, uy);
-      const int x = in.x + 4 * ux, y = in.y + 4 * uy;
-      int p[4][4], o[4][4];
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) p[r][c] = 0;
-      if (valid) luma_pred<k10>(Plane{in.ref, in.rstride, in.pw, in.ph}, in.ral != 0, x + in.bx, y + in.by, in.fx, in.fy, true, p);
-      unit_target<k10>(in, x, y, valid, o);
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) o[r][c] -= p[r][c];
-      // the lanes of a quad share a job and a round: the cross-lane stages of an 8x8 tile see all four
-      uint32_t acc = unit_dist(o, mode, lane, (u & 3) == 0);
-      if (!valid) acc = 0;
-      acc = group_sum(acc, G, lane);   // wave-uniform control flow: every lane of the wave is here
-      if (valid && li == 0) dist[q] += acc;
-    }
-  }
-  __syncthreads();
-  if (t >= nt) return;
-  // ---- the position's cost, the tail, the record ----
-  const int i = t0 + t;
-  const double ml = a.mlambda[j.lambda_id];
-  const int fx = 4 * mvx + direct_dx(cls), fy = 4 * mvy + direct_dy(cls);
-  const uint32_t dsum = dist[t] >> (k10 ? d.bit_depth - 8 : 0);
-  const uint32_t frac_cost = dsum + mv_cost(ml, mv_bits(fx, fy, 0, j.mvp_x, j.mvp_y));
-  uint32_t bits;
-  const uint32_t cost = me_tail(j, ml, frac_cost, fx, fy, bits);
-  const uint32_t status = (last >> 16) | FME_RES_NN_DIRECT;
-  const uint32_t mvw = (uint32_t)(uint16_t)fx | ((uint32_t)(uint16_t)fy << 16);
-  if (d.mv_out) {
-    *(g_di_u4*)(d.mv_out + i) = di_u4{mvw, cost, bits, (uint32_t)cls | (status << 16)};
-  } else {
-    uint8_t* r = reinterpret_cast<uint8_t*>(a.res + i);
-    *(g_di_u4*)r = di_u4{(uint32_t)(uint16_t)mvx | ((uint32_t)(uint16_t)mvy << 16), mvw, direct_half_qtr_word(cls), frac_cost};
-    *(g_di_u2*)(r + 16) = di_u2{cost, bits};
-    *(g_di_u32*)(r + 60) = (last & 0xFFFFu) | (status << 16);
-  }
-}
-
 }  // namespace
 
 static_assert(sizeof(fme_result) == 64 && sizeof(fme_mv_result) == 16, "record layouts");
@@ -430,7 +277,7 @@ hipError_t launch_direct_emi(const DirectArgs& d, hipStream_t s) {
 }
 
 hipError_t launch_direct_eval(const DirectArgs& d, hipStream_t s) {
-  return launch_by_depth(k_direct_eval<false>, k_direct_eval<true>, (d.n + kDiTasks - 1) / kDiTasks, kDiBlock, d, s);
+  return launch_by_depth(k_direct_eval<false, DirectArgs>, k_direct_eval<true, DirectArgs>, (d.n + kDiTasks - 1) / kDiTasks, kDiBlock, d, s);
 }
 
 }  // namespace fme

@@ -101,6 +101,28 @@ def records(jobs, results, state_in=None, label="search", surface=None):
     return r, out
 
 
+def records_from_rows(rows, y):
+    """The SSE.csv records (RECORD_DTYPE[n]) from the rows of fme_nn_inputs (nnfme.predictor
+    NN_ROW_DTYPE: the inputs already resolved on the device) and a label per job, e.g. min_idx of
+    fme_cost_surface_device: records() without the download of the full records and the forward fill.
+    Height / Width are the row's PUHeight / PUWidth, the job's own where it has FME_JOB_EMI (the
+    reference writes a record only for such calls)."""
+    rows = np.asarray(rows)
+    y = np.asarray(y).reshape(-1)
+    if len(y) != len(rows):
+        raise ValueError("records_from_rows: one label per row")
+    r = np.zeros(len(rows), RECORD_DTYPE)
+    for s, name in enumerate(("top_left", "top_center", "top_right", "left")):
+        r[name] = rows["e"][:, s]
+    r["center"] = rows["c"]
+    for s, name in enumerate(("right", "bottom_left", "bottom_center", "bottom_right")):
+        r[name] = rows["e"][:, 4 + s]
+    r["Height"] = rows["pu_h"]
+    r["Width"] = rows["pu_w"]
+    r["y"] = y
+    return r
+
+
 def write_sse_csv(path, recs, append=True):
     """Append records in the reference's text form (`ofstream << a << ',' << ... << endl`)."""
     cols = [np.asarray(recs[n]).astype(np.int64) for n in RECORD_DTYPE.names]
