@@ -480,7 +480,7 @@ int fme_nn_copy_state_device(fme_ctx* c, uint32_t* d_out12, void* stream) {
   }
   // The copy reads the words the last batch's tail wrote: s waits for that batch where it ran on
   // another stream.  The next batch may set or reset those words before its tail, on another
-  // stream again, so it waits for this read first (refine_batch): an event per copy, from a ring,
+  // stream again, so it waits for this read first (hand_state_on): an event per copy, from a ring,
   // recorded once per use; only the latest is ever waited for.
   FME_TRY(wait_batches(c, s));
   HIP_TRY(hipMemcpyAsync(d_out12, c->nn_state.p + 12 * c->state_cur, 12 * sizeof(uint32_t),
@@ -565,7 +565,7 @@ static int enter_stream(fme_ctx* c, hipStream_t s) {
 // rebinding pictures for the next frame never waits for the batch in flight, and the batch stream
 // holds no copy-engine transfer (which would queue behind bulk uploads).  A refinement batch
 // carries them in k_front's kernel argument, and k_front writes the batch's ring entry's copy
-// (refine_batch).  Everything else reads copy 0, which a one-block kernel brings up to date here
+// (batch_begin).  Everything else reads copy 0, which a one-block kernel brings up to date here
 // when the host tables changed since its last upload; its readers are over before this launch
 // (sync_tables waits for the batches in flight, and those read their ring entries' copies).
 static int put_tables(fme_ctx* c, hipStream_t s) {
@@ -601,39 +601,6 @@ int fme::sync_tables(fme_ctx* c, hipStream_t s) {
   return put_tables(c, s);
 }
 
-// What a planned batch (or integer search) does before its first launch: its two events, the waits
-// of its plan that come before the front end, and the fill of the counter blocks when they are in
-// doubt.
-static int batch_begin(fme_ctx* c, const OverlapPlan& plan, hipStream_t s, hipEvent_t* search_end, hipEvent_t* done) {
-  // this batch's events: recorded once per use; before an entry of a ring is recorded again, the
-  // waits queued on its last record (by the three batches after that one) have been passed, which
-  // the end of the last of the three says
-  *search_end = c->search_ev[c->ov.seq % fme_ctx::kDoneRing];
-  *done = c->done_ev[c->ov.seq % fme_ctx::kDoneRing];
-  if (c->ov.seq >= fme_ctx::kDoneRing)
-    HIP_TRY(hipEventSynchronize(c->done_ev[(c->ov.seq + kOvBack) % fme_ctx::kDoneRing]));
-  if (plan.serial) {   // behind every batch in flight
-    if (plan.wait_prev_front) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 1), 0));
-    if (plan.wait_slot) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 2), 0));
-    if (plan.wait_back3) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 3), 0));
-  } else if (plan.wait_front) {
-    // search k - 2 is over: perm and cls of the slot and its counter block are free; the tail of
-    // batch k - 2 may be pending, it reads its own ring entry
-    HIP_TRY(hipStreamWaitEvent(s, search_event(c, 2), 0));
-  } else if (plan.wait_front_end) {
-    HIP_TRY(hipStreamWaitEvent(s, done_event(c, 2), 0));   // batch k - 2 was serialised: all of it
-  }
-  // The counter block is zero: batch k - 2's k_front left it so (the first batches' blocks
-  // fme_create zeroed).  After a batch that was abandoned on the host half-way all blocks are
-  // filled here.  Its launches carry no end event, so the host waits for the context's streams
-  // first (an error path); the batch after this one waits for this one's end (kOvFill), so it does
-  // not start under the fill.
-  if (plan.fill_blocks) {
-    FME_TRY(drain_ctx(c));
-    HIP_TRY(hipMemsetAsync(c->counts.p, 0, kOvBlocks * kCountWords * sizeof(int32_t), s));
-  }
-  return FME_OK;
-}
 
 // Applies a reset / set of the NN state requested since the last batch, in stream order (before the
 // batch's tail, once the stream has waited for the previous batch's tail: that tail writes the
@@ -674,122 +641,235 @@ static int harvest_events(fme_ctx* c, bool wait_all) {
   return FME_OK;
 }
 
-// One batch: front end (classify, scatter and schedule in one kernel) -> search -> NN + tail, all
-// enqueued without waiting for the device.
-// Device validation covers what the host cannot see for device-resident jobs: a job with an
-// unknown PU shape, an unset picture / lambda slot or a key block outside the key buffer makes
-// k_front mark the batch rejected; every later kernel then skips its work.
-// d_jobs null: the batch is d_pjobs / d_key_base (fme_job_packed rows, read in place by every kernel).
-int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_result* d_mv, int n,
-                      hipStream_t s, const fme_job_packed* d_pjobs, const int32_t* d_key_base) {
-  if (c->cfg.nn_mode == 1 && !c->nn_loaded) return fail(FME_E_STATE, "fme_refine_device: nn_mode set but no weights loaded");
-  if (c->cfg.nn_mode == 2 && !c->net_loaded) return fail(FME_E_STATE, "fme_refine_device: nn_mode 2 but no net loaded");
-  if (c->cfg.nn_mode == 2 && c->nn_margin && n > c->nn_margin_cap)
-    return fail(FME_E_INVALID, "fme_refine: %d jobs but the margin output holds %d", n, c->nn_margin_cap);
-  if (c->cfg.nn_mode == 2 && c->nn_logits && n > c->nn_logits_cap)
-    return fail(FME_E_INVALID, "fme_refine: %d jobs but the logit output holds %d", n, c->nn_logits_cap);
-  HIP_TRY(hipSetDevice(c->device));
+// ---- the batch scaffold -------------------------------------------------------------------------
+// A context enqueues four kinds of batch: the ordinary one (refine_batch), the NN-direct one
+// (direct_batch, include/fme_direct.h) and the external predictor's two (inputs_batch and at_batch,
+// include/fme_extern.h).  They are one scaffold with different middles, all enqueued without waiting
+// for the device:
+//   batch_begin    the plan and its waits, the tables, the arguments, k_front
+//   the kind's own launches and event records, with hand_state_on before whatever writes the NN state
+//   batch_end      the end event and the bookkeeping that every reader of a finished batch relies on
+// Only the ordinary batch overlaps its neighbours.  The other three are planned with kOvForeign: a
+// batch number of their own, so that slot, ring entry and counter block are nobody else's and
+// k_front leaves the block after next zeroed, but serial: they start behind every batch in flight
+// (batch_open's waits are sync_tables' wait_batches), the batch after them starts behind their end
+// event, and the front end of the batch after that waits for it too, so nothing runs beside them.
+// The integer search (tz_run) has a front end of its own and shares the inner pieces alone:
+// batch_open and batch_close.
+namespace {
+struct Batch {
+  uint32_t features;   // the kOv* word it is planned and committed with
+  OverlapPlan plan;    // fme_overlap_host.h: its slot, ring entry and counter block, and what its stream waits for
+  hipEvent_t search_end, done;
+  BatchArgs a;
+  WorkBufs w;
+};
+}  // namespace
+
+// What a planned batch (or integer search) does before its first launch: the plan, its two events,
+// the waits of the plan that come before the front end, the fill of the counter blocks when they
+// are in doubt, and its work buffers.  Nothing on the device waits for another batch: every
+// dependency is a stream wait on an earlier batch's event.
+static int batch_open(fme_ctx* c, hipStream_t s, uint32_t features, Batch* b) {
+  b->features = features;
+  b->plan = overlap_plan(c->ov, s, features);
+  const OverlapPlan& plan = b->plan;
+  // this batch's events: recorded once per use; before an entry of a ring is recorded again, the
+  // waits queued on its last record (by the three batches after that one) have been passed, which
+  // the end of the last of the three says
+  b->search_end = c->search_ev[c->ov.seq % fme_ctx::kDoneRing];
+  b->done = c->done_ev[c->ov.seq % fme_ctx::kDoneRing];
+  if (c->ov.seq >= fme_ctx::kDoneRing)
+    HIP_TRY(hipEventSynchronize(c->done_ev[(c->ov.seq + kOvBack) % fme_ctx::kDoneRing]));
+  if (plan.serial) {   // behind every batch in flight
+    if (plan.wait_prev_front) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 1), 0));
+    if (plan.wait_slot) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 2), 0));
+    if (plan.wait_back3) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 3), 0));
+  } else if (plan.wait_front) {
+    // search k - 2 is over: perm and cls of the slot and its counter block are free; the tail of
+    // batch k - 2 may be pending, it reads its own ring entry
+    HIP_TRY(hipStreamWaitEvent(s, search_event(c, 2), 0));
+  } else if (plan.wait_front_end) {
+    HIP_TRY(hipStreamWaitEvent(s, done_event(c, 2), 0));   // batch k - 2 was serialised: all of it
+  }
+  // The counter block is zero: batch k - 2's k_front left it so (the first batches' blocks
+  // fme_create zeroed).  After a batch that was abandoned on the host half-way all blocks are
+  // filled here.  Its launches carry no end event, so the host waits for the context's streams
+  // first (an error path); the batch after this one waits for this one's end (kOvFill), so it does
+  // not start under the fill.
+  if (plan.fill_blocks) {
+    FME_TRY(drain_ctx(c));
+    HIP_TRY(hipMemsetAsync(c->counts.p, 0, kOvBlocks * kCountWords * sizeof(int32_t), s));
+  }
+  b->w = work_bufs(c, plan);
+  return FME_OK;
+}
+
+// Every launch is enqueued: the end event, and the plan is committed (the counter blocks are out of
+// doubt again; a batch that returns before this leaves them to the next batch's fill).
+static int batch_close(fme_ctx* c, hipStream_t s, const Batch& b) {
+  HIP_TRY(hipEventRecord(b.done, s));
+  overlap_commit(c->ov, s, b.features, b.plan);
+  return FME_OK;
+}
+
+// Everything up to and including k_front.  The jobs are fme_job rows, or (d_jobs null) the
+// fme_job_packed rows d_pjobs with d_key_base, read in place by every kernel.  extra: the kind's own
+// feature bits; nn_mode: what the kernels see; zero (may be null): a counter zeroed behind the
+// batch's waits, before its first launch (its last user, an earlier batch, is over); ev_start /
+// ev_front (null when not profiling): recorded before and behind k_front.
+// a.nn_in is the context's binding in every kind: the external predictor's entry points refuse to
+// run while rows are bound (extern_enter), so theirs is null with capacity 0.
+static int batch_begin(fme_ctx* c, const fme_job* d_jobs, const fme_job_packed* d_pjobs, const int32_t* d_key_base,
+                       fme_result* d_res, int n, hipStream_t s, uint32_t extra, int nn_mode, int32_t* zero,
+                       hipEvent_t ev_start, hipEvent_t ev_front, Batch* b) {
   bool grows = false;
   FME_TRY(ensure_work(c, n, &grows));
-  // The plan (fme_overlap_host.h): this batch's slot and counter block, and what its stream waits
-  // for.  Nothing on the device waits for another batch: every dependency is a stream wait on an
-  // earlier batch's end event.
-  const uint32_t features = (c->keys_fresh ? kOvKeys : 0u) | (c->cfg.nn_mode == 2 ? kOvDeepNn : 0u) |
-                            (c->cfg.bit_depth > 8 && c->main10_px ? kOvPx : 0u) |
+  const uint32_t features = extra | (c->keys_fresh ? kOvKeys : 0u) |
                             (d_jobs && d_jobs == c->d_jobs.p ? kOvStaged : 0u) | (grows ? kOvGrow : 0u);
-  const OverlapPlan plan = overlap_plan(c->ov, s, features);
-  hipEvent_t const prev_done = done_event(c, 1), slot_done = done_event(c, 2);
-  hipEvent_t search_end = nullptr, done = nullptr;
-  FME_TRY(enter_stream(c, s));
-  FME_TRY(batch_begin(c, plan, s, &search_end, &done));
-
+  FME_TRY(enter_stream(c, s));   // (touches nothing the plan reads)
+  FME_TRY(batch_open(c, s, features, b));
+  if (zero) HIP_TRY(hipMemsetAsync(zero, 0, sizeof(int32_t), s));
   // The batch's picture / lambda tables travel in k_front's kernel argument; k_front validates
-  // against them and writes them to the ring entry's device copy, which the search and the tail read.
-  PicDesc* const d_pics = c->d_pics.p + (1 + plan.ring) * FME_MAX_PICTURES;
-  double* const d_ml = c->d_mlambda.p + (1 + plan.ring) * FME_MAX_LAMBDAS;
+  // against them and writes them to the ring entry's device copy, which the later kernels read.
+  PicDesc* const d_pics = c->d_pics.p + (1 + b->plan.ring) * FME_MAX_PICTURES;
+  double* const d_ml = c->d_mlambda.p + (1 + b->plan.ring) * FME_MAX_LAMBDAS;
   BatchTables tab;
   for (int i = 0; i < FME_MAX_PICTURES; i++)
     tab.pics[i] = BatchPic{c->pics[i].luma, c->pics[i].stride, c->pics[i].width, c->pics[i].height, 0};
   std::memcpy(tab.ml, c->mlambda, sizeof(c->mlambda));
-  BatchArgs a = batch_args(c, d_jobs, n);
+  BatchArgs& a = b->a;
+  a = batch_args(c, d_jobs, n);
   a.pics = d_pics;
   a.mlambda = d_ml;
   a.pjobs = d_jobs ? nullptr : d_pjobs;
   a.key_base = d_key_base;
-  a.koff = c->koff[plan.ring].p;
+  a.koff = c->koff[b->plan.ring].p;
   a.res = d_res;
-  a.nn_mode = c->cfg.nn_mode ? 1 : 0;
+  a.nn_mode = nn_mode;
   a.nn_in = c->nn_in;
   a.nn_in_cap = c->nn_in_cap;
-  WorkBufs w = work_bufs(c, plan);
-  w.mv_out = d_mv;
+  if (ev_start) HIP_TRY(hipEventRecord(ev_start, s));
+  // the counter block is zero (batch_open); the blocks stay in doubt until every launch of the
+  // batch is enqueued (batch_close)
+  overlap_begin(c->ov);
+  HIP_TRY(launch_front(a, b->w, c->sched_p, tab, d_pics, d_ml, s));
+  if (ev_front) HIP_TRY(hipEventRecord(ev_front, s));
+  return FME_OK;
+}
 
+// Before whatever writes the NN state (a tail, k_nn_rows).  The writers hand the state on: this one
+// runs after the previous batch's, the one dependency between consecutive batches, and a reset /
+// set of the state belongs between the two.  Only an overlapping batch has wait_prev_tail: a serial
+// plan has waited for batch k - 1 before anything (overlap_plan: wait_prev_front = serial && other1,
+// wait_prev_tail = other1 && !wait_prev_front, so serial implies !wait_prev_tail), and kOvForeign
+// makes a plan serial; the three serial kinds enqueue no wait here.
+static int hand_state_on(fme_ctx* c, hipStream_t s, const Batch& b) {
+  if (b.plan.wait_prev_tail) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 1), 0));
+  if (c->state_read_last) {   // a copy of the state the previous writer left (fme_nn_copy_state_device) comes first
+    if (c->state_read_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->state_read_last, 0));
+    c->state_read_last = nullptr;
+  }
+  return apply_pending_state(c, s);
+}
+
+// The end event and what a finished batch leaves: ev_done, last_slot / last_ring
+// (fme_refine_status), keys_fresh, batch_issued, the committed plan and, where the batch wrote the
+// other NN state slot (advanced), state_cur (fme_nn_get_state, fme_nn_copy_state_device).
+static int batch_end(fme_ctx* c, hipStream_t s, const Batch& b, bool advanced) {
+  FME_TRY(batch_close(c, s, b));
+  c->ev_done = b.done;
+  c->last_slot = b.plan.slot;
+  c->last_ring = b.plan.ring;
+  c->keys_fresh = false;
+  c->batch_issued = true;
+  if (advanced) c->state_cur ^= 1;
+  return FME_OK;
+}
+
+// The NN of a batch that runs one is loaded, and the caller's margin / logit outputs hold n jobs.
+static int nn_ready(const fme_ctx* c, int n, const char* name, const char* family) {
+  if (c->cfg.nn_mode == 1 && !c->nn_loaded) return fail(FME_E_STATE, "%s: nn_mode set but no weights loaded", name);
+  if (c->cfg.nn_mode == 2 && !c->net_loaded) return fail(FME_E_STATE, "%s: nn_mode 2 but no net loaded", name);
+  if (c->cfg.nn_mode == 2 && c->nn_margin && n > c->nn_margin_cap)
+    return fail(FME_E_INVALID, "%s: %d jobs but the margin output holds %d", family, n, c->nn_margin_cap);
+  if (c->cfg.nn_mode == 2 && c->nn_logits && n > c->nn_logits_cap)
+    return fail(FME_E_INVALID, "%s: %d jobs but the logit output holds %d", family, n, c->nn_logits_cap);
+  return FME_OK;
+}
+
+// The NN + xMotionEstimation tail of the context's nn_mode, on the batch's stream.
+// (Where it becomes runnable after the next batch's search has started, that search's persistent
+// workgroups hold every wave slot and the tail runs as they drain; on a stream of the highest
+// priority it did the same, since resident workgroups are not displaced: DESIGN.md section 5 "Batch
+// overlap".  The front end of batch k + 2 does not wait for it: it reads this batch's ring entry,
+// the front end writes another.)
+static hipError_t launch_tail(const fme_ctx* c, const Batch& b, hipStream_t s) {
+  return c->cfg.nn_mode == 2
+             ? launch_nn_deep_tail(c->net, c->d_net.p, c->nn_margin, c->nn_logits, b.a, b.w, c->state_cur, c->nn_engine, s)
+             : launch_nn_tail(b.a, b.w, c->d_nn.p, c->state_cur, s);
+}
+
+// The EMI and evaluation kernels' arguments (fme_direct.hip, fme_extern.hip).
+static DirectArgs direct_args(const fme_ctx* c, const Batch& b) {
+  DirectArgs da{};
+  da.a = b.a;
+  da.sched = b.w.sched;
+  da.n = b.a.n;
+  da.bit_depth = c->cfg.bit_depth;
+  return da;
+}
+
+// The ordinary batch: k_front -> search -> NN + tail.
+// Device validation covers what the host cannot see for device-resident jobs: a job with an
+// unknown PU shape, an unset picture / lambda slot or a key block outside the key buffer makes
+// k_front mark the batch rejected; every later kernel then skips its work.
+// d_jobs null: the batch is d_pjobs / d_key_base (fme_job_packed rows).
+int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_result* d_mv, int n,
+                      hipStream_t s, const fme_job_packed* d_pjobs, const int32_t* d_key_base) {
+  FME_TRY(nn_ready(c, n, "fme_refine_device", "fme_refine"));
+  HIP_TRY(hipSetDevice(c->device));
   const bool prof = c->profiling;
   hipEvent_t* ev = nullptr;
-  int eb = 0;
   if (prof) {
     FME_TRY(harvest_events(c, false));
     if (c->ev_head - c->ev_tail == fme_ctx::kEvSets) {   // ring full: wait for the oldest set
       HIP_TRY(hipEventSynchronize(c->ev[c->ev_tail % fme_ctx::kEvSets][6]));
       FME_TRY(harvest_events(c, false));
     }
-    eb = c->ev_head % fme_ctx::kEvSets;
-    ev = c->ev[eb];
-    HIP_TRY(hipEventRecord(ev[0], s));
+    ev = c->ev[c->ev_head % fme_ctx::kEvSets];
   }
-  // the counter block is zero (batch_begin); the blocks stay in doubt until every launch of the
-  // batch is enqueued (overlap_commit)
-  overlap_begin(c->ov);
-  HIP_TRY(launch_front(a, w, c->sched_p, tab, d_pics, d_ml, s));
-  if (prof) HIP_TRY(hipEventRecord(ev[3], s));
+  Batch b;
+  FME_TRY(batch_begin(c, d_jobs, d_pjobs, d_key_base, d_res, n, s,
+                      (c->cfg.nn_mode == 2 ? kOvDeepNn : 0u) | (c->cfg.bit_depth > 8 && c->main10_px ? kOvPx : 0u),
+                      c->cfg.nn_mode ? 1 : 0, nullptr, prof ? ev[0] : nullptr, prof ? ev[3] : nullptr, &b));
+  b.w.mv_out = d_mv;   // (k_front writes no records)
   // the search writes the slot's internal records, which the tail of batch k - 2 reads
-  if (plan.wait_search) HIP_TRY(hipStreamWaitEvent(s, slot_done, 0));
+  if (b.plan.wait_search) HIP_TRY(hipStreamWaitEvent(s, done_event(c, 2), 0));
   if (c->ev_search) HIP_TRY(hipEventRecord(c->ev_search, s));
-  // the lane kernel: every PU shape, one launch on the batch stream (8-bit); the pixel kernel at
-  // bit depth 10 (fme_px.hip)
+  // the lane kernels: every PU shape, one launch on the batch stream, 8-bit (fme_lane.hip) or
+  // 10-bit (fme_lane10.hip); with FME_MAIN10_SEARCH=px the pixel kernels at bit depth 10 (fme_px.hip)
   if (c->cfg.bit_depth > 8) {
     // the small- and large-PU pixel kernels one after the other: side by side on two streams they
     // took 11.5 ms per 1080p frame against 10.5 in series (profiles/r06_ab.log: their LDS and
     // wave slots compete)
     if (c->main10_px)
-      HIP_TRY(launch_search_px(a, w, c->cfg.bit_depth, s, nullptr));
+      HIP_TRY(launch_search_px(b.a, b.w, c->cfg.bit_depth, s, nullptr));
     else
-      HIP_TRY(launch_search_lane10(a, w, s));
+      HIP_TRY(launch_search_lane10(b.a, b.w, s));
   } else {
-    HIP_TRY(launch_search_lane(a, w, c->search_reserve, s));
+    HIP_TRY(launch_search_lane(b.a, b.w, c->search_reserve, s));
   }
   if (prof) HIP_TRY(hipEventRecord(ev[4], s));
-  HIP_TRY(hipEventRecord(search_end, s));   // what the front end of batch k + 2 waits for
-  // the tails hand the NN state on: this one runs after the previous batch's, the one dependency
-  // between consecutive batches; a reset / set of the state belongs between the two
-  if (plan.wait_prev_tail) HIP_TRY(hipStreamWaitEvent(s, prev_done, 0));
-  if (c->state_read_last) {   // a copy of the state the previous tail left (fme_nn_copy_state_device) comes first
-    if (c->state_read_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->state_read_last, 0));
-    c->state_read_last = nullptr;
-  }
-  FME_TRY(apply_pending_state(c, s));
-  // (The tail stays on the batch's stream.  Where it becomes runnable after the next batch's search
-  // has started, that search's persistent workgroups hold every wave slot and the tail runs as they
-  // drain; on a stream of the highest priority it did the same, since resident workgroups are not
-  // displaced: DESIGN.md section 5 "Batch overlap".  The front end of batch k + 2 does not wait for
-  // it: it reads this batch's ring entry, the front end writes another.)
+  HIP_TRY(hipEventRecord(b.search_end, s));   // what the front end of batch k + 2 waits for
+  FME_TRY(hand_state_on(c, s, b));
   if (prof) HIP_TRY(hipEventRecord(ev[5], s));
-  HIP_TRY(c->cfg.nn_mode == 2
-              ? launch_nn_deep_tail(c->net, c->d_net.p, c->nn_margin, c->nn_logits, a, w, c->state_cur, c->nn_engine, s)
-              : launch_nn_tail(a, w, c->d_nn.p, c->state_cur, s));
+  HIP_TRY(launch_tail(c, b, s));
   if (prof) {
     HIP_TRY(hipEventRecord(ev[6], s));
     c->ev_head++;
   }
-  HIP_TRY(hipEventRecord(done, s));
-  c->ev_done = done;
-  c->last_slot = plan.slot;
-  c->last_ring = plan.ring;
-  c->keys_fresh = false;
-  overlap_commit(c->ov, s, features, plan);
-  c->batch_issued = true;
-  if (a.nn_mode) c->state_cur ^= 1;
-  return FME_OK;
+  return batch_end(c, s, b, b.a.nn_mode != 0);
 }
 
 // After a refinement batch: the rejected-job count comes down, one synchronisation, FME_E_INVALID if any.
@@ -801,8 +881,21 @@ int fme::check_rejected(fme_ctx* c, hipStream_t s, const char* name, const char*
   return FME_OK;
 }
 
+// Host arrays: H2D of the jobs into the context's staging buffer, the batch (run), D2H of its
+// output (d_out, in a buffer the caller reserved) and of the rejected-job count, one
+// synchronisation at the end.
+template <class Run>
+static int host_batch(fme_ctx* c, const fme_job* jobs, int n, hipStream_t s, const char* name, void* out,
+                      const void* d_out, size_t out_bytes, Run run) {
+  HIP_TRY(c->d_jobs.reserve(n));
+  HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, (size_t)n * sizeof(fme_job), hipMemcpyHostToDevice, s));
+  FME_TRY(run());
+  HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+  return check_rejected(c, s, name, "with an unsupported PU size or unset picture/lambda/key");
+}
+
 // The *_mv_* device entry points' full records (the search writes them, the tail reads them): context
-// scratch, one buffer per batch slot (the next batch's slot: refine_batch follows at once and plans
+// scratch, one buffer per batch slot (the next batch's slot: the batch follows at once and plans
 // the same batch number).  The host-array entry points and the producers pass c->d_res whichever
 // slot their batch has: they are serialised before and after (kOvStaged), so no batch beside them
 // uses it.
@@ -813,106 +906,35 @@ static int slot_records(fme_ctx* c, int n, fme_result** out) {
   return FME_OK;
 }
 
-// One NN-direct batch (include/fme_direct.h): front end -> EMI kernel -> NN tail -> evaluation
-// kernel, all enqueued without waiting for the device.
-// It takes a batch number like any other, so its slot, ring entry and counter block are nobody
-// else's and k_front leaves the block after next zeroed, but it is planned with kOvForeign: it
-// starts behind every batch in flight (batch_begin's waits are sync_tables' wait_batches), the
-// batch after it starts behind its end event, and the front end of the batch after that waits for
-// its end event too, so nothing overlaps it.  It writes the NN state, the work buffers and the
-// counter block like an ordinary batch and leaves the same bookkeeping: ev_done, last_slot /
-// last_ring (fme_refine_status), state_cur (fme_nn_get_state, fme_nn_copy_state_device),
-// batch_issued, keys_fresh, the noted stream.
+// The NN-direct batch (include/fme_direct.h): k_front -> EMI kernel -> NN tail -> evaluation kernel.
 // The class kernel is the ordinary tail, launched as it is on the records the EMI kernel wrote,
 // whose frac_cost is a placeholder (0): what the tail derives from it (cost, bits) and its mv are
 // overwritten by the evaluation kernel, which follows in stream order, so no reader sees them: the
 // caller's records are complete only behind the evaluation kernel, and the compact form's tail
-// writes the context's internal records, never the caller's array.
+// writes the context's internal records, never the caller's array (mv_out stays null for it).
 int fme::direct_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_result* d_mv, int n,
                       hipStream_t s) {
-  if (c->cfg.nn_mode == 1 && !c->nn_loaded) return fail(FME_E_STATE, "fme_refine_direct: nn_mode set but no weights loaded");
-  if (c->cfg.nn_mode == 2 && !c->net_loaded) return fail(FME_E_STATE, "fme_refine_direct: nn_mode 2 but no net loaded");
-  if (c->cfg.nn_mode == 2 && c->nn_margin && n > c->nn_margin_cap)
-    return fail(FME_E_INVALID, "fme_refine_direct: %d jobs but the margin output holds %d", n, c->nn_margin_cap);
-  if (c->cfg.nn_mode == 2 && c->nn_logits && n > c->nn_logits_cap)
-    return fail(FME_E_INVALID, "fme_refine_direct: %d jobs but the logit output holds %d", n, c->nn_logits_cap);
-  bool grows = false;
-  FME_TRY(ensure_work(c, n, &grows));
-  const uint32_t features = kOvForeign | (c->keys_fresh ? kOvKeys : 0u) | (c->cfg.nn_mode == 2 ? kOvDeepNn : 0u) |
-                            (d_jobs == c->d_jobs.p ? kOvStaged : 0u) | (grows ? kOvGrow : 0u);
-  const OverlapPlan plan = overlap_plan(c->ov, s, features);   // serial
-  hipEvent_t search_end = nullptr, done = nullptr;
-  FME_TRY(enter_stream(c, s));
-  FME_TRY(batch_begin(c, plan, s, &search_end, &done));
-
-  // the tables travel in k_front's argument into the ring entry's copy, as in refine_batch
-  PicDesc* const d_pics = c->d_pics.p + (1 + plan.ring) * FME_MAX_PICTURES;
-  double* const d_ml = c->d_mlambda.p + (1 + plan.ring) * FME_MAX_LAMBDAS;
-  BatchTables tab;
-  for (int i = 0; i < FME_MAX_PICTURES; i++)
-    tab.pics[i] = BatchPic{c->pics[i].luma, c->pics[i].stride, c->pics[i].width, c->pics[i].height, 0};
-  std::memcpy(tab.ml, c->mlambda, sizeof(c->mlambda));
-  BatchArgs a = batch_args(c, d_jobs, n);
-  a.pics = d_pics;
-  a.mlambda = d_ml;
-  a.koff = c->koff[plan.ring].p;
-  a.res = d_res;
-  a.nn_mode = 1;
-  a.nn_in = c->nn_in;
-  a.nn_in_cap = c->nn_in_cap;
-  WorkBufs w = work_bufs(c, plan);   // mv_out null: the tail completes the full records
-  DirectArgs da{};
-  da.a = a;
-  da.sched = w.sched;
-  da.n = n;
-  da.bit_depth = c->cfg.bit_depth;
-
+  FME_TRY(nn_ready(c, n, "fme_refine_direct", "fme_refine_direct"));
   const bool prof = c->profiling;
   hipEvent_t* ev = c->ev_direct;
-  if (prof) {
+  if (prof)
     for (int k = 0; k < 5; k++)
       if (!ev[k]) HIP_TRY(hipEventCreate(&ev[k]));
-    HIP_TRY(hipEventRecord(ev[0], s));
-  }
-  overlap_begin(c->ov);   // the counter blocks are in doubt until every launch is enqueued
-  HIP_TRY(launch_front(a, w, c->sched_p, tab, d_pics, d_ml, s));
-  if (prof) HIP_TRY(hipEventRecord(ev[1], s));
+  Batch b;
+  FME_TRY(batch_begin(c, d_jobs, nullptr, nullptr, d_res, n, s, kOvForeign | (c->cfg.nn_mode == 2 ? kOvDeepNn : 0u), 1,
+                      nullptr, prof ? ev[0] : nullptr, prof ? ev[1] : nullptr, &b));
+  DirectArgs da = direct_args(c, b);
   HIP_TRY(launch_direct_emi(da, s));
   if (prof) HIP_TRY(hipEventRecord(ev[2], s));
-  HIP_TRY(hipEventRecord(search_end, s));
-  if (c->state_read_last) {   // a copy of the state the previous tail left comes first
-    if (c->state_read_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->state_read_last, 0));
-    c->state_read_last = nullptr;
-  }
-  FME_TRY(apply_pending_state(c, s));
-  HIP_TRY(c->cfg.nn_mode == 2
-              ? launch_nn_deep_tail(c->net, c->d_net.p, c->nn_margin, c->nn_logits, a, w, c->state_cur, c->nn_engine, s)
-              : launch_nn_tail(a, w, c->d_nn.p, c->state_cur, s));
+  HIP_TRY(hipEventRecord(b.search_end, s));
+  FME_TRY(hand_state_on(c, s, b));
+  HIP_TRY(launch_tail(c, b, s));
   if (prof) HIP_TRY(hipEventRecord(ev[3], s));
   da.mv_out = d_mv;
   HIP_TRY(launch_direct_eval(da, s));
   if (prof) HIP_TRY(hipEventRecord(ev[4], s));
   c->direct_timed = prof;
-  HIP_TRY(hipEventRecord(done, s));
-  c->ev_done = done;
-  c->last_slot = plan.slot;
-  c->last_ring = plan.ring;
-  c->keys_fresh = false;
-  overlap_commit(c->ov, s, features, plan);
-  c->batch_issued = true;
-  c->state_cur ^= 1;
-  return FME_OK;
-}
-
-// Host arrays, as refine_host: H2D of the jobs, the batch, D2H of the records and of the
-// rejected-job count, one synchronisation at the end.
-static int direct_host(fme_ctx* c, const fme_job* jobs, fme_result* res, int n, hipStream_t s) {
-  HIP_TRY(c->d_jobs.reserve(n));
-  HIP_TRY(c->d_res.reserve(n));
-  HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, (size_t)n * sizeof(fme_job), hipMemcpyHostToDevice, s));
-  FME_TRY(direct_batch(c, c->d_jobs.p, c->d_res.p, nullptr, n, s));
-  HIP_TRY(hipMemcpyAsync(res, c->d_res.p, (size_t)n * sizeof(fme_result), hipMemcpyDeviceToHost, s));
-  return check_rejected(c, s, "fme_refine_direct", "with an unsupported PU size or unset picture/lambda/key");
+  return batch_end(c, s, b, true);
 }
 
 // The direct entry points' common start: the argument check (fme_direct_host.h); *run: enqueue.
@@ -929,116 +951,54 @@ static int direct_enter(fme_ctx* c, const void* jobs, const void* out, int n, co
 }
 
 // ---- the external predictor (include/fme_extern.h) -----------------------------------------------
-// Both batches below are a direct batch cut at the class, and are planned and booked like one
-// (direct_batch above): a batch number of their own, kOvForeign, so they start behind every batch in
-// flight and nothing overlaps them; ev_done, last_slot / last_ring, batch_issued, keys_fresh and the
-// noted stream are left as by any batch.
-
-// What the two share: the plan, the waits, the tables, k_front.
-struct ExternBatch {
-  OverlapPlan plan;
-  uint32_t features;
-  hipEvent_t search_end, done;
-  BatchArgs a;
-  WorkBufs w;
-};
-// zero (may be null): a counter zeroed behind the batch's waits, before its first launch.
-static int extern_begin(fme_ctx* c, const fme_job* d_jobs, fme_result* d_rec, int n, hipStream_t s, int32_t* zero,
-                        ExternBatch* b) {
-  bool grows = false;
-  FME_TRY(ensure_work(c, n, &grows));
-  b->features = kOvForeign | (c->keys_fresh ? kOvKeys : 0u) | (d_jobs == c->d_jobs.p ? kOvStaged : 0u) |
-                (grows ? kOvGrow : 0u);
-  b->plan = overlap_plan(c->ov, s, b->features);   // serial
-  b->search_end = b->done = nullptr;
-  FME_TRY(enter_stream(c, s));
-  FME_TRY(batch_begin(c, b->plan, s, &b->search_end, &b->done));
-  if (zero) HIP_TRY(hipMemsetAsync(zero, 0, sizeof(int32_t), s));   // (its last user, an earlier batch, is over)
-  PicDesc* const d_pics = c->d_pics.p + (1 + b->plan.ring) * FME_MAX_PICTURES;
-  double* const d_ml = c->d_mlambda.p + (1 + b->plan.ring) * FME_MAX_LAMBDAS;
-  BatchTables tab;
-  for (int i = 0; i < FME_MAX_PICTURES; i++)
-    tab.pics[i] = BatchPic{c->pics[i].luma, c->pics[i].stride, c->pics[i].width, c->pics[i].height, 0};
-  std::memcpy(tab.ml, c->mlambda, sizeof(c->mlambda));
-  b->a = batch_args(c, d_jobs, n);
-  b->a.pics = d_pics;
-  b->a.mlambda = d_ml;
-  b->a.koff = c->koff[b->plan.ring].p;
-  b->a.res = d_rec;
-  b->a.nn_mode = 1;
-  b->a.nn_in = nullptr;   // (none bound: the entry points refuse otherwise)
-  b->a.nn_in_cap = 0;
-  b->w = work_bufs(c, b->plan);
-  const bool prof = c->profiling;
-  if (prof) {
+// Both batches are a direct batch cut at the class.  Their profiling events: [0] / [1] around
+// k_front, [2] behind the EMI kernel, [3] behind the rows kernel, [4] behind the evaluation.
+static int extern_events(fme_ctx* c) {
+  if (c->profiling)
     for (auto& e : c->ev_extern)
       if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c->ev_extern[0], s));
-  }
-  c->extern_timed = false;
-  overlap_begin(c->ov);   // the counter blocks are in doubt until every launch is enqueued
-  HIP_TRY(launch_front(b->a, b->w, c->sched_p, tab, d_pics, d_ml, s));
-  if (prof) HIP_TRY(hipEventRecord(c->ev_extern[1], s));
+  c->extern_timed = false;   // until the batch is enqueued in full
   return FME_OK;
-}
-static int extern_end(fme_ctx* c, hipStream_t s, const ExternBatch& b, unsigned phases) {
-  c->extern_phases = phases;
-  c->extern_timed = c->profiling;
-  HIP_TRY(hipEventRecord(b.done, s));
-  c->ev_done = b.done;
-  c->last_slot = b.plan.slot;
-  c->last_ring = b.plan.ring;
-  c->keys_fresh = false;
-  overlap_commit(c->ov, s, b.features, b.plan);
-  c->batch_issued = true;
-  return FME_OK;
-}
-static DirectArgs extern_direct_args(const fme_ctx* c, const ExternBatch& b, int n) {
-  DirectArgs da{};
-  da.a = b.a;
-  da.sched = b.w.sched;
-  da.n = n;
-  da.bit_depth = c->cfg.bit_depth;
-  return da;
 }
 
-// One inputs batch: front end -> EMI kernel (on d_rec, context-internal records) -> rows kernel.  It
-// hands the NN state on like a tail, in every nn_mode: it waits for a copy of the state in flight,
-// applies a pending set / reset, writes the other state slot and flips state_cur.
+// The inputs batch: k_front -> EMI kernel (on d_rec, context-internal records) -> rows kernel.  It
+// hands the NN state on like a tail, in every nn_mode: it writes the other state slot.
 static int inputs_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_rec, fme_nn_row* d_rows, int n, hipStream_t s) {
-  ExternBatch b;
-  FME_TRY(extern_begin(c, d_jobs, d_rec, n, s, nullptr, &b));
   const bool prof = c->profiling;
-  HIP_TRY(launch_direct_emi(extern_direct_args(c, b, n), s));
-  if (prof) HIP_TRY(hipEventRecord(c->ev_extern[2], s));
+  hipEvent_t* ev = c->ev_extern;
+  FME_TRY(extern_events(c));
+  Batch b;
+  FME_TRY(batch_begin(c, d_jobs, nullptr, nullptr, d_rec, n, s, kOvForeign, 1, nullptr, prof ? ev[0] : nullptr,
+                      prof ? ev[1] : nullptr, &b));
+  HIP_TRY(launch_direct_emi(direct_args(c, b), s));
+  if (prof) HIP_TRY(hipEventRecord(ev[2], s));
   HIP_TRY(hipEventRecord(b.search_end, s));
-  if (c->state_read_last) {   // a copy of the state the previous tail left comes first
-    if (c->state_read_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->state_read_last, 0));
-    c->state_read_last = nullptr;
-  }
-  FME_TRY(apply_pending_state(c, s));
+  FME_TRY(hand_state_on(c, s, b));
   const bool slot_reset = c->cfg.nn_mode == 2 && c->net_loaded && (c->net.input_flags & FME_NN_IN_SLOT_RESET);
   HIP_TRY(launch_nn_rows(b.a, b.w, d_rows, c->state_cur, slot_reset, s));
-  if (prof) HIP_TRY(hipEventRecord(c->ev_extern[3], s));
-  FME_TRY(extern_end(c, s, b, 3u));
-  c->state_cur ^= 1;
-  return FME_OK;
+  if (prof) HIP_TRY(hipEventRecord(ev[3], s));
+  c->extern_phases = 3u;
+  c->extern_timed = prof;
+  return batch_end(c, s, b, true);
 }
 
-// One evaluation batch: front end -> EMI kernel unless the caller brought rows -> evaluation at the
+// The evaluation batch: k_front -> EMI kernel unless the caller brought rows -> evaluation at the
 // caller's classes.  d_res: the full records (with d_mv and no rows: context-internal ones the EMI
 // kernel writes; with d_mv and rows: null).  The NN state is not touched.
 static int at_batch(fme_ctx* c, const fme_job* d_jobs, const fme_nn_row* d_rows, const uint8_t* d_cls,
                     fme_result* d_res, fme_mv_result* d_mv, int n, hipStream_t s) {
   HIP_TRY(c->d_ext_refused.reserve(1));
-  ExternBatch b;
-  FME_TRY(extern_begin(c, d_jobs, d_res, n, s, c->d_ext_refused.p, &b));
   const bool prof = c->profiling;
+  hipEvent_t* ev = c->ev_extern;
+  FME_TRY(extern_events(c));
+  Batch b;
+  FME_TRY(batch_begin(c, d_jobs, nullptr, nullptr, d_res, n, s, kOvForeign, 1, c->d_ext_refused.p,
+                      prof ? ev[0] : nullptr, prof ? ev[1] : nullptr, &b));
   ExternArgs x{};
-  x.d = extern_direct_args(c, b, n);
+  x.d = direct_args(c, b);
   if (!d_rows) {
     HIP_TRY(launch_direct_emi(x.d, s));
-    if (prof) HIP_TRY(hipEventRecord(c->ev_extern[2], s));
+    if (prof) HIP_TRY(hipEventRecord(ev[2], s));
   }
   HIP_TRY(hipEventRecord(b.search_end, s));
   x.d.mv_out = d_mv;
@@ -1046,11 +1006,14 @@ static int at_batch(fme_ctx* c, const fme_job* d_jobs, const fme_nn_row* d_rows,
   x.n = n;
   x.bit_depth = c->cfg.bit_depth;
   HIP_TRY(launch_at_eval(x, s));
-  if (prof) HIP_TRY(hipEventRecord(c->ev_extern[4], s));
-  FME_TRY(extern_end(c, s, b, d_rows ? 4u : 5u));
+  if (prof) HIP_TRY(hipEventRecord(ev[4], s));
+  c->extern_phases = d_rows ? 4u : 5u;
+  c->extern_timed = prof;
+  FME_TRY(batch_end(c, s, b, false));
   c->ev_at_done = b.done;
   return FME_OK;
 }
+
 
 // The families' common start: the argument check (fme_extern_host.h); *run: enqueue.
 static int extern_enter(fme_ctx* c, int rq, int n, const char* name, bool* run) {
@@ -1071,13 +1034,10 @@ int fme_nn_inputs(fme_ctx* c, const fme_job* jobs, fme_nn_row* rows, int n, void
   FME_TRY(extern_enter(c, extern_inputs_request(c, jobs, rows, n, c && c->nn_in), n, "fme_nn_inputs", &run));
   if (!run) return FME_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(c->d_jobs.reserve(n));
   HIP_TRY(c->d_res.reserve(n));
   HIP_TRY(c->d_ext_rows.reserve(n));
-  HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, (size_t)n * sizeof(fme_job), hipMemcpyHostToDevice, s));
-  FME_TRY(inputs_batch(c, c->d_jobs.p, c->d_res.p, c->d_ext_rows.p, n, s));
-  HIP_TRY(hipMemcpyAsync(rows, c->d_ext_rows.p, (size_t)n * sizeof(fme_nn_row), hipMemcpyDeviceToHost, s));
-  return check_rejected(c, s, "fme_nn_inputs", "with an unsupported PU size or unset picture/lambda/key");
+  return host_batch(c, jobs, n, s, "fme_nn_inputs", rows, c->d_ext_rows.p, (size_t)n * sizeof(fme_nn_row),
+                    [&] { return inputs_batch(c, c->d_jobs.p, c->d_res.p, c->d_ext_rows.p, n, s); });
 }
 
 int fme_nn_inputs_device(fme_ctx* c, const fme_job* d_jobs, fme_nn_row* d_rows, int n, void* stream) {
@@ -1159,7 +1119,11 @@ int fme_extern_last_ms(fme_ctx* c, float ms[4]) {
 int fme_refine_direct(fme_ctx* c, const fme_job* jobs, fme_result* res, int n, void* stream) {
   bool run;
   FME_TRY(direct_enter(c, jobs, res, n, "fme_refine_direct", &run));
-  return run ? direct_host(c, jobs, res, n, static_cast<hipStream_t>(stream)) : FME_OK;
+  if (!run) return FME_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(c->d_res.reserve(n));
+  return host_batch(c, jobs, n, s, "fme_refine_direct", res, c->d_res.p, (size_t)n * sizeof(fme_result),
+                    [&] { return direct_batch(c, c->d_jobs.p, c->d_res.p, nullptr, n, s); });
 }
 
 int fme_refine_direct_device(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, int n, void* stream) {
@@ -1508,18 +1472,18 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   hipStream_t s = static_cast<hipStream_t>(stream);
   FME_TRY(ensure_work(c, n));
   FME_TRY(sync_tables(c, s));
-  BatchArgs a = batch_args(c, d_jobs, n);
-  a.nn_in = c->nn_in;   // FME_JOB_NN_IN jobs (the B producer's bi rounds) pass k_classify with their rows
-  a.nn_in_cap = c->nn_in_cap;
   // The integer search is planned like a refinement batch (kOvForeign): behind every batch in
   // flight, with a batch number of its own, so that its slot and counter block are nobody else's,
   // the block comes round zeroed again (its scatter zeroes the block of the batch after next, as
   // k_front does) and the batches after it wait for its events, both recorded at its end.  It
   // reads copy 0 of the tables.
-  const OverlapPlan plan = overlap_plan(c->ov, s, kOvForeign);
-  hipEvent_t search_end = nullptr, done = nullptr;
-  FME_TRY(batch_begin(c, plan, s, &search_end, &done));
-  WorkBufs w = work_bufs(c, plan);
+  Batch bt;
+  FME_TRY(batch_open(c, s, kOvForeign, &bt));
+  BatchArgs& a = bt.a;
+  a = batch_args(c, d_jobs, n);
+  a.nn_in = c->nn_in;   // FME_JOB_NN_IN jobs (the B producer's bi rounds) pass k_classify with their rows
+  a.nn_in_cap = c->nn_in_cap;
+  const WorkBufs& w = bt.w;
   if (c->profiling) {
     if (!c->ev_tz[0]) {
       HIP_TRY(hipEventCreate(&c->ev_tz[0]));
@@ -1586,10 +1550,8 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   HIP_TRY(hipStreamWaitEvent(s, c->ev_join2, 0));
   if (c->profiling) HIP_TRY(hipEventRecord(c->ev_tz[1], s));
   c->tz_timed = c->profiling;
-  HIP_TRY(hipEventRecord(search_end, s));
-  HIP_TRY(hipEventRecord(done, s));
-  overlap_commit(c->ov, s, kOvForeign, plan);
-  return FME_OK;
+  HIP_TRY(hipEventRecord(bt.search_end, s));
+  return batch_close(c, s, bt);
 }
 
 static int tz_run_host(fme_ctx* c, fme_job* jobs, const fme_tz_ext* ext, uint32_t* sad, int n, void* stream,
@@ -1660,24 +1622,17 @@ int fme_integer_search_last_ms(fme_ctx* c, float* ms) {
   return FME_OK;
 }
 
-// Host arrays: H2D of the jobs, the batch, D2H of the outputs and of the rejected-job count,
-// one synchronisation at the end.
 static int refine_host(fme_ctx* c, const fme_job* jobs, fme_result* res, fme_mv_result* mv, int n, void* stream,
                        const char* name) {
   if (!c || (n > 0 && (!jobs || (!res && !mv)))) return fail(FME_E_INVALID, "%s: null argument", name);
   if (n <= 0) return n == 0 ? FME_OK : fail(FME_E_INVALID, "%s: n = %d", name, n);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(c->d_jobs.reserve(n));
   HIP_TRY(c->d_res.reserve(n));
   if (mv) HIP_TRY(c->d_mv.reserve(n));
-  HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, (size_t)n * sizeof(fme_job), hipMemcpyHostToDevice, s));
-  FME_TRY(refine_batch(c, c->d_jobs.p, c->d_res.p, mv ? c->d_mv.p : nullptr, n, s));
-  if (mv)
-    HIP_TRY(hipMemcpyAsync(mv, c->d_mv.p, (size_t)n * sizeof(fme_mv_result), hipMemcpyDeviceToHost, s));
-  else
-    HIP_TRY(hipMemcpyAsync(res, c->d_res.p, (size_t)n * sizeof(fme_result), hipMemcpyDeviceToHost, s));
-  return check_rejected(c, s, name, "with an unsupported PU size or unset picture/lambda/key");
+  return host_batch(c, jobs, n, s, name, mv ? (void*)mv : (void*)res, mv ? (const void*)c->d_mv.p : (const void*)c->d_res.p,
+                    (size_t)n * (mv ? sizeof(fme_mv_result) : sizeof(fme_result)),
+                    [&] { return refine_batch(c, c->d_jobs.p, c->d_res.p, mv ? c->d_mv.p : nullptr, n, s); });
 }
 
 int fme_refine(fme_ctx* c, const fme_job* jobs, fme_result* res, int n, void* stream) {

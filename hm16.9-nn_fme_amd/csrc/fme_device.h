@@ -539,7 +539,9 @@ __device__ __forceinline__ bool nn_writes_c(const fme_job& j) { return (j.flags 
 // getCost(mvBits))) + getCost(ruiBits), fW 0.5 for a bi-pred iteration; double like
 // TComRdCost::getCost, converted with gcc/x86-64's (Distortion)(double) semantics.  tail_job and the
 // NN-direct evaluation (fme_direct.hip) call it.  (k_nn_deep_tail keeps its own statement of the
-// same lines: through this function its load of frac_cost moves and its code changes.)
+// same lines: through this function its load of frac_cost moves and its code changes.  For the same
+// reason it keeps its own statement of the carried-input rule, which nn_carried below states for
+// k_nn_tail and k_nn_rows: the deep tail is the one deliberate exception to both.)
 __device__ __forceinline__ uint32_t me_tail(const fme_job& j, double ml, uint32_t frac_cost, int fx, int fy,
                                             uint32_t& bits) {
   const uint32_t mvb = simd::mv_bits(fx, fy, 0, j.mvp_x, j.mvp_y);
@@ -640,6 +642,70 @@ __device__ __forceinline__ void writer_scan_wave(const BatchArgs& a, const int (
     const unsigned long long m = __ballot(run[f] >= 0) & below;
     src[f] = m ? wbase + 63 - __clzll(m) : prev[f];   // a writer in the wave is later than any before it
   }
+}
+
+// NN_pred()'s carried inputs as job i sees them: the one statement of the rule for k_nn_tail
+// (tail_job) and k_nn_rows.  (k_nn_deep_tail is the deliberate exception and keeps its own: its
+// invalid lanes run on through the net, and it reads the job's own pushes from memory.)
+// Per carried field (array_e slot s < 8; field 8: C and the PU size), src[] being the last writer
+// at or before the job (writer_scan_wave): the job's own push, from its record in registers
+// (own_emi, own_c); else the record of the earlier writer; else the incoming state st_in.
+// `written` is the state's mask with the fields some job of the batch wrote added.
+// slot_reset (FME_NN_IN_SLOT_RESET, as in k_nn_deep_tail): the slots hold this job's own pushes and
+// 0 elsewhere, and all count as written.
+struct NnCarried {
+  uint32_t e[8], c, ph, pw, written;
+};
+__device__ __forceinline__ void nn_carried(const BatchArgs& a, const WorkBufs& w, const uint32_t* st_in, int i,
+                                           const fme_job& j, const int (&src)[9], const uint32_t (&own_emi)[8],
+                                           uint32_t own_c, bool slot_reset, NnCarried& v) {
+  v.written = st_in[11];
+#pragma unroll
+  for (int s = 0; s < 8; s++) {
+    if (slot_reset) {
+      v.e[s] = src[s] == i ? own_emi[s] : 0u;
+      v.written |= 1u << s;
+    } else if (src[s] == i) {
+      v.e[s] = own_emi[s];
+      v.written |= 1u << s;
+    } else if (src[s] >= 0) {
+      v.e[s] = search_rec(a, w, src[s])->emi[s];
+      v.written |= 1u << s;
+    } else {
+      v.e[s] = st_in[s];
+    }
+  }
+  if (src[8] == i) {
+    v.c = own_c;
+    v.ph = j.h;
+    v.pw = j.w;
+    v.written |= 0x100u;
+  } else if (src[8] >= 0) {
+    v.c = search_rec(a, w, src[8])->c;
+    load_job_wh(a, src[8], v.pw, v.ph);
+    v.written |= 0x100u;
+  } else {
+    v.c = st_in[8];
+    v.ph = st_in[9];
+    v.pw = st_in[10];
+  }
+}
+// FME_RES_NN_STALE: the job did not push all of its own inputs; FME_RES_NN_UNINIT: a carried field
+// that nothing has written yet, in this batch or before it.
+__device__ __forceinline__ uint32_t nn_carried_status(bool writes_c, uint32_t own_n_emi, const NnCarried& v) {
+  uint32_t status = 0;
+  if (!writes_c || own_n_emi < 8) status |= FME_RES_NN_STALE;
+  if ((v.written & 0x1FFu) != 0x1FFu) status |= FME_RES_NN_UNINIT;
+  return status;
+}
+// The batch's last job carries what it saw to the next batch: the twelve state words.
+__device__ __forceinline__ void nn_carry_on(uint32_t* st_out, const NnCarried& v) {
+#pragma unroll
+  for (int s = 0; s < 8; s++) st_out[s] = v.e[s];
+  st_out[8] = v.c;
+  st_out[9] = v.ph;
+  st_out[10] = v.pw;
+  st_out[11] = v.written;
 }
 
 // A batch k_classify rejected: every job is marked, nothing else is written, and the NN state

@@ -3,11 +3,11 @@
 // context-internal records, then k_nn_rows; fme_refine_at* is k_front, k_direct_emi unless the
 // caller brings rows, then the evaluation (inputs_batch, at_batch, fme_api.cpp).
 //
-// k_nn_rows: the NN tail (fme_kernels.hip k_nn_tail) without the net.  One lane per job, one wave
-// per workgroup, the last-writer scan over the wave and backwards through its scan block
-// (writer_scan_wave, with k_front's blk_prefix as the carry-in), the same three-way choice per
-// carried field (the job's own push, an earlier job's record, the incoming state) and the same two
-// status conditions; what tail_job hands to nn_forward goes into the job's row instead, as four
+// k_nn_rows: one lane per job, one wave per workgroup, the last-writer scan over the wave and
+// backwards through its scan block (writer_scan_wave, with k_front's blk_prefix as the carry-in),
+// then the carried-input rule, which fme_device.h states once for this kernel and for the NN tail
+// (nn_carried, nn_carried_status, nn_carry_on; k_nn_deep_tail is the one deliberate exception and
+// keeps its own statement).  What tail_job hands to nn_forward goes into the job's row, as four
 // 16-byte stores, and the last job writes the state.  Unlike the tail it does so in every nn_mode.
 //
 // The evaluation: k_direct_eval<k10, ExternArgs> (fme_direct_eval.h), the direct batch's kernel with
@@ -68,57 +68,17 @@ __global__ __launch_bounds__(kRowsNT) void k_nn_rows(BatchArgs a, WorkBufs w, fm
   int src[9];
   writer_scan_wave(a, run, w.blk_prefix + (wbase / kJobsPerScanBlock) * 9, wbase, src);
   if (!valid) return;
-  // ---- what tail_job resolves before it calls the net ----
   const uint32_t own_emi[8] = {r1.w, r2.x, r2.y, r2.z, r2.w, r3.x, r3.y, r3.z};
   const uint32_t own_c = r1.z, own_n_emi = r3.w & 0xFFu;
-  uint32_t e[8];
-  uint32_t written = st_in[11];
-#pragma unroll
-  for (int s = 0; s < 8; s++) {
-    if (slot_reset) {   // FME_NN_IN_SLOT_RESET (k_nn_deep_tail): this job's own pushes, 0 elsewhere
-      e[s] = src[s] == i ? own_emi[s] : 0u;
-      written |= 1u << s;
-    } else if (src[s] == i) {
-      e[s] = own_emi[s];
-      written |= 1u << s;
-    } else if (src[s] >= 0) {
-      e[s] = search_rec(a, w, src[s])->emi[s];
-      written |= 1u << s;
-    } else {
-      e[s] = st_in[s];
-    }
-  }
-  uint32_t c, ph, pw;
-  if (src[8] == i) {
-    c = own_c;
-    ph = j.h;
-    pw = j.w;
-    written |= 0x100u;
-  } else if (src[8] >= 0) {
-    c = search_rec(a, w, src[8])->c;
-    load_job_wh(a, src[8], pw, ph);
-    written |= 0x100u;
-  } else {
-    c = st_in[8];
-    ph = st_in[9];
-    pw = st_in[10];
-  }
-  uint32_t status = 0;
-  if (!wr || own_n_emi < 8) status |= FME_RES_NN_STALE;
-  if ((written & 0x1FFu) != 0x1FFu) status |= FME_RES_NN_UNINIT;
+  NnCarried v;
+  nn_carried(a, w, st_in, i, j, src, own_emi, own_c, slot_reset != 0, v);
+  const uint32_t status = nn_carried_status(wr, own_n_emi, v);
   g_di_u4* o = (g_di_u4*)(rows + i);
-  o[0] = di_u4{e[0], e[1], e[2], e[3]};
-  o[1] = di_u4{e[4], e[5], e[6], e[7]};
-  o[2] = di_u4{c, ph, pw, r0.x};   // r0.x: mv_int_x, mv_int_y
+  o[0] = di_u4{v.e[0], v.e[1], v.e[2], v.e[3]};
+  o[1] = di_u4{v.e[4], v.e[5], v.e[6], v.e[7]};
+  o[2] = di_u4{v.c, v.ph, v.pw, r0.x};   // r0.x: mv_int_x, mv_int_y
   o[3] = di_u4{own_n_emi | (wr ? 0x100u : 0u) | (status << 16), 0u, 0u, 0u};
-  if (i == a.n - 1) {   // carry the global state to the next batch
-#pragma unroll
-    for (int s = 0; s < 8; s++) st_out[s] = e[s];
-    st_out[8] = c;
-    st_out[9] = ph;
-    st_out[10] = pw;
-    st_out[11] = written;
-  }
+  if (i == a.n - 1) nn_carry_on(st_out, v);
 }
 
 }  // namespace

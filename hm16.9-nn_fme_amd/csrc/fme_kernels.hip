@@ -641,48 +641,13 @@ __device__ __forceinline__ void tail_job(const BatchArgs& a, const WorkBufs& w, 
   int offx, offy, cls = 255;
   uint16_t status = 0;
   if (a.nn_mode) {
-    uint32_t e[8];
-    uint32_t written = st_in[11];
-#pragma unroll
-    for (int s = 0; s < 8; s++) {
-      if (src[s] == i) {
-        e[s] = own_emi[s];
-        written |= 1u << s;
-      } else if (src[s] >= 0) {
-        e[s] = search_rec(a, w, src[s])->emi[s];
-        written |= 1u << s;
-      } else {
-        e[s] = st_in[s];
-      }
-    }
-    uint32_t c, ph, pw;
-    if (src[8] == i) {
-      c = own_c;
-      ph = j.h;
-      pw = j.w;
-      written |= 0x100u;
-    } else if (src[8] >= 0) {
-      c = search_rec(a, w, src[8])->c;
-      load_job_wh(a, src[8], pw, ph);
-      written |= 0x100u;
-    } else {
-      c = st_in[8];
-      ph = st_in[9];
-      pw = st_in[10];
-    }
-    cls = nn_forward(nnp_g, e, c, (int)ph, (int)pw);
-    if (!nn_writes_c(j) || own_n_emi < 8) status |= FME_RES_NN_STALE;
-    if ((written & 0x1FFu) != 0x1FFu) status |= FME_RES_NN_UNINIT;
+    NnCarried v;
+    nn_carried(a, w, st_in, i, j, src, own_emi, own_c, false, v);
+    cls = nn_forward(nnp_g, v.e, v.c, (int)v.ph, (int)v.pw);
+    status = (uint16_t)nn_carried_status(nn_writes_c(j), own_n_emi, v);
     offx = cls % 7 - 3;
     offy = cls / 7 - 3;
-    if (i == a.n - 1) {  // carry the global state to the next batch
-#pragma unroll
-      for (int s = 0; s < 8; s++) st_out[s] = e[s];
-      st_out[8] = c;
-      st_out[9] = ph;
-      st_out[10] = pw;
-      st_out[11] = written;
-    }
+    if (i == a.n - 1) nn_carry_on(st_out, v);
   } else {
     const int8_t hx = (int8_t)(r0.z & 0xFF), hy = (int8_t)((r0.z >> 8) & 0xFF);
     const int8_t qx = (int8_t)((r0.z >> 16) & 0xFF), qy = (int8_t)(r0.z >> 24);
