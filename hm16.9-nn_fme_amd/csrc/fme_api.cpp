@@ -73,8 +73,8 @@ int fme_create(int device, const fme_config* cfg, fme_ctx** out_ctx) {
   HIP_TRY(hipMemset(c->counts.p, 0, kOvBlocks * kCountWords * sizeof(int32_t)));
   HIP_TRY(c->d_sched.reserve(kOvRing));
   HIP_TRY(hipMemset(c->d_sched.p, 0, kOvRing * sizeof(Schedule)));
-  for (auto& e : c->done_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : c->search_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& e : c->done_ev) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+  for (auto& e : c->search_ev) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
   c->sched_p = sched_params();
   {
     const char* m10 = std::getenv("FME_MAIN10_SEARCH");
@@ -158,68 +158,6 @@ int fme_destroy(fme_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)srv_stop(c);
   (void)hipDeviceSynchronize();
-  for (int i = 0; i < FME_MAX_PICTURES; i++)
-    if (c->pic_owned[i] && c->pics[i].luma) (void)hipFree(const_cast<uint8_t*>(c->pics[i].luma));
-  for (int i = 0; i < FME_MAX_PICTURES; i++)
-    if (c->chroma_owned[i]) (void)hipFree(c->chroma_owned[i]);
-  c->d_mc_jobs.release(); c->d_mc_planes.release(); c->d_mc_invalid.release(); c->d_mc_wp.release();
-  c->d_tz_ext.release(); c->d_tz_sad.release(); c->d_tz_nn_in.release();
-  c->d_amvp.release(); c->d_amvp_sad.release(); c->d_bikey.release(); c->d_key_invalid.release(); c->d_ch_i32.release(); c->d_tz_emi.release();
-  c->h_pi_tasks.release(); c->h_pi_tsad.release(); c->h_pi_jobs.release(); c->h_pi_ext.release();
-  c->h_pi_idx.release(); c->h_pi_psrc.release(); c->h_pi_mv.release(); c->h_pi_last.release();
-  c->h_pi_ures.release(); c->h_pi_seq.release(); c->h_pi_rs.release(); c->h_pi_rows.release();
-  c->d_pi_jobs.release(); c->d_pi_ext.release(); c->d_pi_idx.release();
-  for (auto& e : c->ev_tz)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->ev_mc)
-    if (e) (void)hipEventDestroy(e);
-  c->d_pe_tasks.release(); c->d_pe_dist.release(); c->d_pe_invalid.release();
-  for (auto& e : c->ev_pe)
-    if (e) (void)hipEventDestroy(e);
-  c->d_sse_tasks.release(); c->d_sse_out.release(); c->d_sse_invalid.release();
-  for (auto& e : c->ev_sse)
-    if (e) (void)hipEventDestroy(e);
-  c->d_surf_jobs.release(); c->d_surf_probe.release(); c->d_surf_out.release(); c->d_surf_pick.release();
-  c->d_surf_invalid.release();
-  for (auto& e : c->ev_surf)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->ev_direct)
-    if (e) (void)hipEventDestroy(e);
-  c->d_ext_rows.release(); c->d_ext_cls.release(); c->d_ext_refused.release();
-  for (auto& e : c->ev_extern)
-    if (e) (void)hipEventDestroy(e);
-  c->d_pics.release(); c->d_mlambda.release(); c->d_keys.release(); c->d_nn.release(); c->d_net.release();
-  c->d_jobs.release(); c->d_res.release(); c->d_res1.release(); c->d_mv.release();
-  for (int b = 0; b < kOvSlots; b++) {
-    c->cls[b].release(); c->perm[b].release();
-  }
-  for (int r = 0; r < kOvRing; r++) {
-    c->koff[r].release(); c->blk_agg[r].release(); c->blk_prefix[r].release();
-  }
-  c->counts.release(); c->nn_state.release();
-  c->d_sched.release();
-  for (auto& e : c->done_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->search_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->state_read_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->stage) (void)hipHostFree(c->stage);
-  if (c->single_stream) (void)hipStreamDestroy(c->single_stream);
-  if (c->box) (void)hipHostFree(c->box);
-  if (c->srv_stream) (void)hipStreamDestroy(c->srv_stream);
-  if (c->h_counts) (void)hipHostFree(c->h_counts);
-  if (c->h_tab) (void)hipHostFree(c->h_tab);
-  for (auto& e : c->tab_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& set : c->ev)
-    for (auto& e : set)
-      if (e) (void)hipEventDestroy(e);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join2) (void)hipEventDestroy(c->ev_join2);
-  if (c->aux2) (void)hipStreamDestroy(c->aux2);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->aux) (void)hipStreamDestroy(c->aux);
   delete c;
   return FME_OK;
 }
@@ -485,8 +423,8 @@ int fme_nn_copy_state_device(fme_ctx* c, uint32_t* d_out12, void* stream) {
   FME_TRY(wait_batches(c, s));
   HIP_TRY(hipMemcpyAsync(d_out12, c->nn_state.p + 12 * c->state_cur, 12 * sizeof(uint32_t),
                          hipMemcpyDeviceToDevice, s));
-  hipEvent_t& e = c->state_read_ev[c->state_reads++ % fme_ctx::kDoneRing];
-  if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  Event& e = c->state_read_ev[c->state_reads++ % fme_ctx::kDoneRing];
+  if (!e) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(e, s));
   c->state_read_last = e;
   c->state_read_stream = s;
@@ -582,7 +520,7 @@ static int put_tables(fme_ctx* c, hipStream_t s) {
     void* d = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&d, p, 0));
     c->h_tab_dev = static_cast<TablesSlot*>(d);
-    for (auto& e : c->tab_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& e : c->tab_ev) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
   }
   const int k = c->tab_next;
   c->tab_next = (k + 1) % fme_ctx::kTabSlots;
@@ -601,6 +539,76 @@ int fme::sync_tables(fme_ctx* c, hipStream_t s) {
   return put_tables(c, s);
 }
 
+// ---- what the side launches share (fme_ctx.h) ----------------------------------------------------
+int LaunchTimer::ensure(const fme_ctx* c) {
+  if (c->profiling)
+    for (auto& e : ev)
+      if (!e) HIP_TRY(hipEventCreate(&e.h));
+  return FME_OK;
+}
+int LaunchTimer::begin(const fme_ctx* c, hipStream_t s) {
+  FME_TRY(ensure(c));
+  if (c->profiling) HIP_TRY(hipEventRecord(ev[0], s));
+  return FME_OK;
+}
+int LaunchTimer::end(const fme_ctx* c, hipStream_t s) {
+  if (c->profiling) HIP_TRY(hipEventRecord(ev[1], s));
+  timed = c->profiling;
+  return FME_OK;
+}
+int fme::timer_last_ms(fme_ctx* c, LaunchTimer fme_ctx::*timer, const char* name, const char* what, float* ms) {
+  if (!c || !ms) return fail(FME_E_INVALID, "%s: null argument", name);
+  const LaunchTimer& t = c->*timer;
+  if (!t.timed) return fail(FME_E_STATE, "%s: no profiled %s", name, what);
+  HIP_TRY(hipEventSynchronize(t.ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, t.ev[0], t.ev[1]));
+  return FME_OK;
+}
+
+int InvalidCounter::zero(hipStream_t s) {
+  HIP_TRY(d.reserve(1));
+  HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(int32_t), s));
+  stream = s;
+  return FME_OK;
+}
+int fme::invalid_count(fme_ctx* c, InvalidCounter fme_ctx::*counter, const char* name, bool drain_all) {
+  if (!c) return fail(FME_E_INVALID, "%s: null ctx", name);
+  const InvalidCounter& k = c->*counter;
+  if (!k.d.p) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  int32_t v = 0;
+  if (drain_all) FME_TRY(drain_ctx(c));
+  else HIP_TRY(hipStreamSynchronize(k.stream));
+  HIP_TRY(hipMemcpy(&v, k.d.p, sizeof(v), hipMemcpyDeviceToHost));
+  return v;
+}
+
+const char* fme::pred_task_problem(const fme_ctx* c, PredKind kind, int x, int y, int w, int h, unsigned flags,
+                                   const uint8_t* ref_id, unsigned org_id, int width, int height) {
+  const bool mc = kind == kPredMc, sse = kind == kPredSse;
+  if (w < 4 || h < 4 || w > 64 || h > 64 || (w & 3) || (h & 3)) return sse ? "block size" : "PU size";
+  const unsigned lists = FME_MC_L0 | FME_MC_L1, more = mc ? FME_MC_WP : sse ? 0u : FME_PE_LOSSLESS;
+  if (!(flags & lists) || (flags & ~(lists | more))) return "list flags";
+  if (!mc) {   // the picture is the original's
+    if (org_id >= FME_MAX_PICTURES || !c->pics[org_id].luma) return "original picture";
+    const PicDesc& o = c->pics[org_id];
+    if (sse && (!o.cb || !o.cr)) return "original picture without chroma planes";
+    width = o.width;
+    height = o.height;
+  }
+  if (x + w > width || y + h > height) return sse ? "block outside the picture" : "PU outside the picture";
+  for (int l = 0; l < 2; l++) {
+    if (!(flags & (1u << l))) continue;
+    if (ref_id[l] >= FME_MAX_PICTURES) return mc ? "reference id" : "reference picture";
+    const PicDesc& p = c->pics[ref_id[l]];
+    if (mc && (!p.luma || !p.cb || !p.cr)) return "reference picture without luma + chroma";
+    if (!p.luma) return "reference picture";
+    if (sse && (!p.cb || !p.cr)) return "reference picture without chroma planes";
+    if (p.width != width || p.height != height) return "reference picture dimensions";
+  }
+  return nullptr;
+}
+
 
 // Applies a reset / set of the NN state requested since the last batch, in stream order (before the
 // batch's tail, once the stream has waited for the previous batch's tail: that tail writes the
@@ -617,7 +625,7 @@ static int apply_pending_state(fme_ctx* c, hipStream_t s) {
 static int harvest_events(fme_ctx* c, bool wait_all) {
   while (c->ev_tail != c->ev_head) {
     const int b = c->ev_tail % fme_ctx::kEvSets;
-    hipEvent_t* e = c->ev[b];
+    const Event* e = c->ev[b];
     if (wait_all) {
       HIP_TRY(hipEventSynchronize(e[6]));
     } else {
@@ -830,7 +838,7 @@ int fme::refine_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
   FME_TRY(nn_ready(c, n, "fme_refine_device", "fme_refine"));
   HIP_TRY(hipSetDevice(c->device));
   const bool prof = c->profiling;
-  hipEvent_t* ev = nullptr;
+  const Event* ev = nullptr;
   if (prof) {
     FME_TRY(harvest_events(c, false));
     if (c->ev_head - c->ev_tail == fme_ctx::kEvSets) {   // ring full: wait for the oldest set
@@ -916,10 +924,10 @@ int fme::direct_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_
                       hipStream_t s) {
   FME_TRY(nn_ready(c, n, "fme_refine_direct", "fme_refine_direct"));
   const bool prof = c->profiling;
-  hipEvent_t* ev = c->ev_direct;
+  Event* ev = c->ev_direct;
   if (prof)
     for (int k = 0; k < 5; k++)
-      if (!ev[k]) HIP_TRY(hipEventCreate(&ev[k]));
+      if (!ev[k]) HIP_TRY(hipEventCreate(&ev[k].h));
   Batch b;
   FME_TRY(batch_begin(c, d_jobs, nullptr, nullptr, d_res, n, s, kOvForeign | (c->cfg.nn_mode == 2 ? kOvDeepNn : 0u), 1,
                       nullptr, prof ? ev[0] : nullptr, prof ? ev[1] : nullptr, &b));
@@ -956,7 +964,7 @@ static int direct_enter(fme_ctx* c, const void* jobs, const void* out, int n, co
 static int extern_events(fme_ctx* c) {
   if (c->profiling)
     for (auto& e : c->ev_extern)
-      if (!e) HIP_TRY(hipEventCreate(&e));
+      if (!e) HIP_TRY(hipEventCreate(&e.h));
   c->extern_timed = false;   // until the batch is enqueued in full
   return FME_OK;
 }
@@ -965,7 +973,7 @@ static int extern_events(fme_ctx* c) {
 // hands the NN state on like a tail, in every nn_mode: it writes the other state slot.
 static int inputs_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_rec, fme_nn_row* d_rows, int n, hipStream_t s) {
   const bool prof = c->profiling;
-  hipEvent_t* ev = c->ev_extern;
+  const Event* ev = c->ev_extern;
   FME_TRY(extern_events(c));
   Batch b;
   FME_TRY(batch_begin(c, d_jobs, nullptr, nullptr, d_rec, n, s, kOvForeign, 1, nullptr, prof ? ev[0] : nullptr,
@@ -989,7 +997,7 @@ static int at_batch(fme_ctx* c, const fme_job* d_jobs, const fme_nn_row* d_rows,
                     fme_result* d_res, fme_mv_result* d_mv, int n, hipStream_t s) {
   HIP_TRY(c->d_ext_refused.reserve(1));
   const bool prof = c->profiling;
-  hipEvent_t* ev = c->ev_extern;
+  const Event* ev = c->ev_extern;
   FME_TRY(extern_events(c));
   Batch b;
   FME_TRY(batch_begin(c, d_jobs, nullptr, nullptr, d_res, n, s, kOvForeign, 1, c->d_ext_refused.p,
@@ -1104,7 +1112,7 @@ int fme_extern_last_ms(fme_ctx* c, float ms[4]) {
   if (!c || !ms) return fail(FME_E_INVALID, "fme_extern_last_ms: null argument");
   if (!c->extern_timed) return fail(FME_E_STATE, "fme_extern_last_ms: no profiled batch of fme_nn_inputs* / fme_refine_at*");
   HIP_TRY(hipSetDevice(c->device));
-  hipEvent_t* e = c->ev_extern;
+  const Event* e = c->ev_extern;
   const unsigned ph = c->extern_phases;
   const int last = (ph & 4u) ? 4 : 3;
   HIP_TRY(hipEventSynchronize(e[last]));
@@ -1145,7 +1153,7 @@ int fme_refine_direct_last_ms(fme_ctx* c, float ms[4]) {
   if (!c || !ms) return fail(FME_E_INVALID, "fme_refine_direct_last_ms: null argument");
   if (!c->direct_timed) return fail(FME_E_STATE, "fme_refine_direct_last_ms: no profiled direct batch");
   HIP_TRY(hipSetDevice(c->device));
-  hipEvent_t* e = c->ev_direct;
+  const Event* e = c->ev_direct;
   HIP_TRY(hipEventSynchronize(e[4]));
   for (int k = 0; k < 3; k++) HIP_TRY(hipEventElapsedTime(&ms[k], e[1 + k], e[2 + k]));
   HIP_TRY(hipEventElapsedTime(&ms[3], e[0], e[4]));
@@ -1484,12 +1492,7 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   a.nn_in = c->nn_in;   // FME_JOB_NN_IN jobs (the B producer's bi rounds) pass k_classify with their rows
   a.nn_in_cap = c->nn_in_cap;
   const WorkBufs& w = bt.w;
-  if (c->profiling) {
-    if (!c->ev_tz[0]) {
-      HIP_TRY(hipEventCreate(&c->ev_tz[0]));
-      HIP_TRY(hipEventCreate(&c->ev_tz[1]));
-    }
-  }
+  FME_TRY(c->tz_timer.ensure(c));   // (its events are made before the blocks are in doubt)
   // in doubt until everything is enqueued (an invalid job ends the call after the first pass)
   overlap_begin(c->ov);
   HIP_TRY(launch_classify(a, w, s));
@@ -1509,15 +1512,15 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   ta.sad = d_sad;
   ta.emi_mv = d_emi;
   ta.nn_in = d_nn_in;
-  if (c->profiling) HIP_TRY(hipEventRecord(c->ev_tz[0], s));
+  FME_TRY(c->tz_timer.begin(c, s));
   // the three unit-shape kernels are latency-bound and independent: 4x8 and 8x4 units on the two
   // auxiliary streams, 8x8 units on the caller's stream, joined before returning
   // the integer search's own auxiliary streams (the refinement batch uses none)
-  if (!c->aux) HIP_TRY(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-  if (!c->aux2) HIP_TRY(hipStreamCreateWithFlags(&c->aux2, hipStreamNonBlocking));
-  if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-  if (!c->ev_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  if (!c->ev_join2) HIP_TRY(hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));
+  if (!c->aux) HIP_TRY(hipStreamCreateWithFlags(&c->aux.h, hipStreamNonBlocking));
+  if (!c->aux2) HIP_TRY(hipStreamCreateWithFlags(&c->aux2.h, hipStreamNonBlocking));
+  if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork.h, hipEventDisableTiming));
+  if (!c->ev_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_join.h, hipEventDisableTiming));
+  if (!c->ev_join2) HIP_TRY(hipEventCreateWithFlags(&c->ev_join2.h, hipEventDisableTiming));
   // the groups (np > 0 here: a job that passed k_classify names a bound picture)
   const size_t words = 8 + 12 * (size_t)np;
   if (c->d_tzp.cap < words || c->d_tzp_perm.cap < (size_t)n) {
@@ -1548,8 +1551,7 @@ int fme::tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* 
   HIP_TRY(hipEventRecord(c->ev_join2, c->aux2));
   HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
   HIP_TRY(hipStreamWaitEvent(s, c->ev_join2, 0));
-  if (c->profiling) HIP_TRY(hipEventRecord(c->ev_tz[1], s));
-  c->tz_timed = c->profiling;
+  FME_TRY(c->tz_timer.end(c, s));
   HIP_TRY(hipEventRecord(bt.search_end, s));
   return batch_close(c, s, bt);
 }
@@ -1615,11 +1617,7 @@ int fme_integer_search_ring(fme_ctx* c, fme_job* jobs, const fme_tz_ext* ext, ui
 }
 
 int fme_integer_search_last_ms(fme_ctx* c, float* ms) {
-  if (!c || !ms) return fail(FME_E_INVALID, "fme_integer_search_last_ms: null argument");
-  if (!c->tz_timed) return fail(FME_E_STATE, "fme_integer_search_last_ms: no profiled integer search");
-  HIP_TRY(hipEventSynchronize(c->ev_tz[1]));
-  HIP_TRY(hipEventElapsedTime(ms, c->ev_tz[0], c->ev_tz[1]));
-  return FME_OK;
+  return timer_last_ms(c, &fme_ctx::tz_timer, "fme_integer_search_last_ms", "integer search", ms);
 }
 
 static int refine_host(fme_ctx* c, const fme_job* jobs, fme_result* res, fme_mv_result* mv, int n, void* stream,
@@ -1652,7 +1650,7 @@ static int ensure_stage(fme_ctx* c) {
   void* d = nullptr;
   HIP_TRY(hipHostGetDevicePointer(&d, p, 0));
   c->stage_dev = static_cast<uint8_t*>(d);
-  HIP_TRY(hipStreamCreateWithFlags(&c->single_stream, hipStreamNonBlocking));
+  HIP_TRY(hipStreamCreateWithFlags(&c->single_stream.h, hipStreamNonBlocking));
   std::memset(c->stage, 0, sizeof(SingleStage));
   return FME_OK;
 }
@@ -1700,7 +1698,7 @@ static int srv_open(fme_ctx* c) {
   void* d = nullptr;
   HIP_TRY(hipHostGetDevicePointer(&d, p, 0));
   c->box_dev = static_cast<SrvBox*>(d);
-  HIP_TRY(hipStreamCreateWithFlags(&c->srv_stream, hipStreamNonBlocking));
+  HIP_TRY(hipStreamCreateWithFlags(&c->srv_stream.h, hipStreamNonBlocking));
   int khz = 0;
   if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0)
     c->srv_khz = (uint64_t)khz;
@@ -1905,24 +1903,13 @@ int fme_search_kernel_of_shape(int width, int height) {
 
 // ---- motion compensation ---------------------------------------------------------------------
 static const char* mc_job_problem(const fme_ctx* c, const fme_mc_job& j, int width, int height) {
-  if (j.w < 4 || j.h < 4 || j.w > 64 || j.h > 64 || (j.w & 3) || (j.h & 3)) return "PU size";
-  if (!(j.flags & (FME_MC_L0 | FME_MC_L1)) || (j.flags & ~(FME_MC_L0 | FME_MC_L1 | FME_MC_WP))) return "list flags";
-  if ((int)j.x + j.w > width || (int)j.y + j.h > height) return "PU outside the picture";
-  for (int l = 0; l < 2; l++) {
-    if (!(j.flags & (1u << l))) continue;
-    if (j.ref_id[l] >= FME_MAX_PICTURES) return "reference id";
-    const PicDesc& p = c->pics[j.ref_id[l]];
-    if (!p.luma || !p.cb || !p.cr) return "reference picture without luma + chroma";
-    if (p.width != width || p.height != height) return "reference picture dimensions";
-  }
-  return nullptr;
+  return pred_task_problem(c, kPredMc, j.x, j.y, j.w, j.h, j.flags, j.ref_id, 0, width, height);
 }
 
 static int mc_launch(fme_ctx* c, const fme_mc_job* d_jobs, int n, uint8_t* y, int ys, uint8_t* cb, uint8_t* cr,
                      int cs, int width, int height, hipStream_t s) {
-  HIP_TRY(c->d_mc_invalid.reserve(1));
-  HIP_TRY(hipMemsetAsync(c->d_mc_invalid.p, 0, sizeof(int32_t), s));
-  if (int e = sync_tables(c, s)) return e;
+  FME_TRY(c->mc_invalid.zero(s));
+  FME_TRY(sync_tables(c, s));
   if (!c->wp_init) {   // the default weights: 1 << 0, offset 0
     for (auto& l : c->h_wp)
       for (auto& p : l)
@@ -1941,24 +1928,16 @@ static int mc_launch(fme_ctx* c, const fme_mc_job* d_jobs, int n, uint8_t* y, in
   a.y = y;
   a.cb = cb;
   a.cr = cr;
-  a.invalid = c->d_mc_invalid.p;
+  a.invalid = c->mc_invalid.d.p;
   a.n = n;
   a.y_stride = ys;
   a.c_stride = cs;
   a.width = width;
   a.height = height;
   a.bit_depth = c->cfg.bit_depth;   // 10: uint16 planes, strides in samples (k_mc<true>)
-  if (c->profiling) {
-    if (!c->ev_mc[0]) {
-      HIP_TRY(hipEventCreate(&c->ev_mc[0]));
-      HIP_TRY(hipEventCreate(&c->ev_mc[1]));
-    }
-    HIP_TRY(hipEventRecord(c->ev_mc[0], s));
-  }
+  FME_TRY(c->mc_timer.begin(c, s));
   HIP_TRY(launch_mc(a, s));
-  if (c->profiling) HIP_TRY(hipEventRecord(c->ev_mc[1], s));
-  c->mc_timed = c->profiling;
-  return FME_OK;
+  return c->mc_timer.end(c, s);
 }
 
 static int mc_check_planes(const void* y, int ys, const void* cb, const void* cr, int cs, int width, int height) {
@@ -2007,13 +1986,9 @@ int fme_motion_compensate_device(fme_ctx* c, const fme_mc_job* d_jobs, int n, ui
 }
 
 int fme_mc_invalid_count(fme_ctx* c) {
-  if (!c) return fail(FME_E_INVALID, "fme_mc_invalid_count: null ctx");
-  if (!c->d_mc_invalid.p) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  int32_t v = 0;
-  FME_TRY(drain_ctx(c));   // this context's streams only
-  HIP_TRY(hipMemcpy(&v, c->d_mc_invalid.p, sizeof(v), hipMemcpyDeviceToHost));
-  return v;
+  // drains every stream the context used, where the other three wait for the last launch's: callers
+  // have had that wider barrier since this replaced a device synchronisation, so it stays
+  return invalid_count(c, &fme_ctx::mc_invalid, "fme_mc_invalid_count", true);
 }
 
 int fme_set_wp(fme_ctx* c, int list, int ref_id, const fme_wp_param* p) {
@@ -2034,11 +2009,7 @@ int fme_set_wp(fme_ctx* c, int list, int ref_id, const fme_wp_param* p) {
 }
 
 int fme_mc_last_ms(fme_ctx* c, float* ms) {
-  if (!c || !ms) return fail(FME_E_INVALID, "fme_mc_last_ms: null argument");
-  if (!c->mc_timed) return fail(FME_E_STATE, "fme_mc_last_ms: no profiled motion compensation");
-  HIP_TRY(hipEventSynchronize(c->ev_mc[1]));
-  HIP_TRY(hipEventElapsedTime(ms, c->ev_mc[0], c->ev_mc[1]));
-  return FME_OK;
+  return timer_last_ms(c, &fme_ctx::mc_timer, "fme_mc_last_ms", "motion compensation", ms);
 }
 
 int fme_set_profiling(fme_ctx* c, int enable) {
@@ -2046,7 +2017,7 @@ int fme_set_profiling(fme_ctx* c, int enable) {
   HIP_TRY(hipSetDevice(c->device));
   if (enable && !c->events_made) {
     for (auto& set : c->ev)
-      for (auto& e : set) HIP_TRY(hipEventCreate(&e));
+      for (auto& e : set) HIP_TRY(hipEventCreate(&e.h));
     c->events_made = true;
   }
   if (!enable) FME_TRY(harvest_events(c, true));

@@ -10,10 +10,14 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "fme_device.h"
 #include "fme_overlap_host.h"
+
+struct fme_ctx;
 
 namespace fme {
 
@@ -36,11 +40,20 @@ int fail(int code, const char* fmt, ...);
   } while (0)
 
 // Device memory (DevBuf) or pinned host memory (HostBuf: the producers' transfer buffers, full-rate
-// DMA and no page faults on the buffers of the next call), grown on demand.
+// DMA and no page faults on the buffers of the next call), grown on demand and freed with its owner.
 template <typename T, bool kPinned>
 struct Buf {
   T* p = nullptr;
   size_t cap = 0;
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  Buf& operator=(Buf&& o) noexcept {
+    std::swap(p, o.p), std::swap(cap, o.cap);
+    return *this;
+  }
+  ~Buf() { release(); }
   hipError_t reserve(size_t n) {
     if (n <= cap) return hipSuccess;
     release();
@@ -58,6 +71,55 @@ struct Buf {
 };
 template <typename T> using DevBuf = Buf<T, false>;
 template <typename T> using HostBuf = Buf<T, true>;
+
+// An event / a stream that its holder created and destroys.  h is public and the handle converts
+// implicitly, so hipEventCreate(&e.h), hipEventRecord(e, s) and `if (!e)` read as with a raw handle.
+struct Event {
+  hipEvent_t h = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : h(o.h) { o.h = nullptr; }
+  Event& operator=(Event&& o) noexcept {
+    std::swap(h, o.h);
+    return *this;
+  }
+  ~Event() {
+    if (h) (void)hipEventDestroy(h);
+  }
+  operator hipEvent_t() const { return h; }
+};
+struct Stream {
+  hipStream_t h = nullptr;
+  Stream() = default;
+  Stream(Stream&& o) noexcept : h(o.h) { o.h = nullptr; }
+  Stream& operator=(Stream&& o) noexcept {
+    std::swap(h, o.h);
+    return *this;
+  }
+  ~Stream() {
+    if (h) (void)hipStreamDestroy(h);
+  }
+  operator hipStream_t() const { return h; }
+};
+static_assert(!std::is_copy_constructible<DevBuf<int>>::value && !std::is_copy_assignable<HostBuf<int>>::value &&
+                  !std::is_copy_constructible<Event>::value && !std::is_copy_constructible<Stream>::value,
+              "owners of device resources are move-only: a copy would free twice");
+
+// The timing of a side launch (motion compensation, prediction error, SSE, cost surface, integer
+// search): two events around the last launch made with profiling on (fme_api.cpp).
+struct LaunchTimer {
+  Event ev[2];
+  bool timed = false;                        // the last launch was profiled
+  int ensure(const fme_ctx* c);              // the events exist once profiling is on (begin calls it)
+  int begin(const fme_ctx* c, hipStream_t s);   // before the launch
+  int end(const fme_ctx* c, hipStream_t s);     // behind it
+};
+// The count of the tasks a side launch's kernel skipped: one device word, zeroed in stream order
+// before the launch, and the stream of that launch.
+struct InvalidCounter {
+  DevBuf<int32_t> d;
+  hipStream_t stream = nullptr;   // borrowed: the caller's stream of the last launch
+  int zero(hipStream_t s);
+};
 
 // f(lo, hi) over [0, n) in up to 8 host threads (the producers' per-request loops; the caller's
 // thread takes the first slice).
@@ -108,7 +170,7 @@ struct fme_ctx {
   static constexpr int kTabSlots = 16;
   fme::TablesSlot* h_tab = nullptr;
   fme::TablesSlot* h_tab_dev = nullptr;
-  hipEvent_t tab_ev[kTabSlots] = {};
+  fme::Event tab_ev[kTabSlots];
   bool tab_used[kTabSlots] = {};
   int tab_next = 0;
   fme::DevBuf<int16_t> d_keys;
@@ -144,13 +206,13 @@ struct fme_ctx {
   // the batches' events: batch k records search_ev[k % kDoneRing] behind its search launch and
   // done_ev[k % kDoneRing] after its tail, each once
   static constexpr int kDoneRing = 16;
-  hipEvent_t done_ev[kDoneRing] = {};
-  hipEvent_t search_ev[kDoneRing] = {};
+  fme::Event done_ev[kDoneRing];
+  fme::Event search_ev[kDoneRing];
   // fme_nn_copy_state_device's reads of the carried state: the next batch's set / reset waits for the latest
-  hipEvent_t state_read_ev[kDoneRing] = {};
+  fme::Event state_read_ev[kDoneRing];
   long long state_reads = 0;
-  hipEvent_t state_read_last = nullptr;
-  hipStream_t state_read_stream = nullptr;
+  hipEvent_t state_read_last = nullptr;      // borrowed: one of state_read_ev
+  hipStream_t state_read_stream = nullptr;   // borrowed: the caller's
   int last_slot = 0;                // slot and ring entry of the last batch (fme_refine_status, fme_debug_front)
   int last_ring = 0;
   bool keys_fresh = false;          // the key buffer was written since the last batch
@@ -160,52 +222,44 @@ struct fme_ctx {
   uint32_t pending_state[12] = {};
   fme::DevBuf<fme::Schedule> d_sched;     // [kOvRing], built by k_front each batch
   fme::SchedParams sched_p{};
-  int32_t* h_counts = nullptr; // pinned
+  int32_t* h_counts = nullptr; // pinned (freed by ~fme_ctx, like h_tab, stage and box)
 
   // motion compensation: owned chroma planes (cb then cr, one allocation per slot), staging
   uint8_t* chroma_owned[FME_MAX_PICTURES]{};
   size_t chroma_bytes[FME_MAX_PICTURES]{};
   fme::DevBuf<fme_mc_job> d_mc_jobs;
   fme::DevBuf<uint8_t> d_mc_planes;
-  fme::DevBuf<int32_t> d_mc_invalid;
+  fme::InvalidCounter mc_invalid;
   // weighted prediction (fme_set_wp): [list][picture][Y, Cb, Cr], uploaded before a launch when changed
   fme_wp_param h_wp[2][FME_MAX_PICTURES][3] = {};
   bool wp_init = false, wp_dirty = true;
   fme::DevBuf<fme_wp_param> d_mc_wp;
-  hipEvent_t ev_mc[2] = {nullptr, nullptr};
-  bool mc_timed = false;
+  fme::LaunchTimer mc_timer;
   // prediction error / merge estimation (fme_merge.cpp): staging for the host entry points, the
-  // skipped-task counter, the stream of the last launch, timing events
+  // skipped-task counter, the timer
   fme::DevBuf<fme_pe_task> d_pe_tasks;
   fme::DevBuf<uint32_t> d_pe_dist;
-  fme::DevBuf<int32_t> d_pe_invalid;
+  fme::InvalidCounter pe_invalid;
   std::vector<fme_pe_task> h_pe_tasks;
   std::vector<uint32_t> h_pe_dist;
-  hipStream_t pe_stream = nullptr;
-  hipEvent_t ev_pe[2] = {nullptr, nullptr};
-  bool pe_timed = false;
+  fme::LaunchTimer pe_timer;
   // skip check (fme_skip.cpp): the same for the SSE launch
   fme::DevBuf<fme_sse_task> d_sse_tasks;
   fme::DevBuf<uint32_t> d_sse_out;       // [n][3]
-  fme::DevBuf<int32_t> d_sse_invalid;
+  fme::InvalidCounter sse_invalid;
   std::vector<fme_sse_task> h_sse_tasks;
   std::vector<uint32_t> h_sse_out;
-  hipStream_t sse_stream = nullptr;
-  hipEvent_t ev_sse[2] = {nullptr, nullptr};
-  bool sse_timed = false;
-  // cost surface (fme_surface.cpp): staging for the host entry point, the invalid-job counter, the
-  // stream of the last launch, timing events
+  fme::LaunchTimer sse_timer;
+  // cost surface (fme_surface.cpp): staging for the host entry point, the invalid-job counter, the timer
   fme::DevBuf<fme_job> d_surf_jobs;
   fme::DevBuf<uint8_t> d_surf_probe;     // [n][2]
   fme::DevBuf<fme_surface> d_surf_out;
   fme::DevBuf<fme_surface_pick> d_surf_pick;
-  fme::DevBuf<int32_t> d_surf_invalid;
-  hipStream_t surf_stream = nullptr;
-  hipEvent_t ev_surf[2] = {nullptr, nullptr};
-  bool surf_timed = false;
+  fme::InvalidCounter surf_invalid;
+  fme::LaunchTimer surf_timer;
   // NN-direct batches (include/fme_direct.h): timing events of the last one with profiling on: start,
   // front end, EMI, class and evaluation kernel ends
-  hipEvent_t ev_direct[5] = {};
+  fme::Event ev_direct[5];
   bool direct_timed = false;
   // the external predictor (include/fme_extern.h): staging of the host forms' rows and classes, the
   // count of the jobs the last fme_refine_at* batch refused one by one and that batch's end event (one
@@ -214,16 +268,15 @@ struct fme_ctx {
   fme::DevBuf<fme_nn_row> d_ext_rows;
   fme::DevBuf<uint8_t> d_ext_cls;
   fme::DevBuf<int32_t> d_ext_refused;
-  hipEvent_t ev_at_done = nullptr;
-  hipEvent_t ev_extern[5] = {};
+  hipEvent_t ev_at_done = nullptr;   // borrowed: one of done_ev
+  fme::Event ev_extern[5];
   unsigned extern_phases = 0;
   bool extern_timed = false;
-  // integer search: staging for the host entry point, timing events
+  // integer search: staging for the host entry point, the timer
   fme::DevBuf<fme_tz_ext> d_tz_ext;
   fme::DevBuf<uint32_t> d_tz_sad;
   fme::DevBuf<uint32_t> d_tz_nn_in;   // staging of fme_integer_search_ring's NN input rows
-  hipEvent_t ev_tz[2] = {nullptr, nullptr};
-  bool tz_timed = false;
+  fme::LaunchTimer tz_timer;
   // phase wall times of the last producer call (fme_pred_inter_phases)
   double pi_ms[FME_PI_PHASES] = {};
   // predInterSearch producer: m_integerMv2Nx2N[REF_PIC_LIST_0][k] (TEncSearch.h:118), AMVP staging
@@ -261,17 +314,18 @@ struct fme_ctx {
   // pinned, device-mapped host memory.
   struct SingleStage* stage = nullptr;
   uint8_t* stage_dev = nullptr;
-  hipStream_t single_stream = nullptr;
+  fme::Stream single_stream;
   uint32_t single_seq = 0;
   // The single-call server (fme_server.hip) behind fme_frac_dif_single and the master net's
   // fme_nn_pred_single: its mailbox in pinned, device-mapped host memory, its own stream.
   fme::SrvBox* box = nullptr;
   fme::SrvBox* box_dev = nullptr;
-  hipStream_t srv_stream = nullptr;
+  fme::Stream srv_stream;
   bool srv_running = false;
   bool srv_orphan = false;      // a wait on the instance timed out: it may still run on srv_stream
   // the streams this context's batches were issued on (note_stream): a buffer that a queued launch
-  // may still read is regrown only after those streams have drained, not the whole device
+  // may still read is regrown only after those streams have drained, not the whole device (borrowed:
+  // the callers' streams and the context's own)
   static constexpr int kMaxStreams = 8;
   hipStream_t used_streams[kMaxStreams] = {};
   int n_used_streams = 0;
@@ -291,12 +345,12 @@ struct fme_ctx {
   static constexpr int kEvSets = 32;
   bool profiling = false;
   bool events_made = false;
-  hipEvent_t ev[kEvSets][kEv] = {};
+  fme::Event ev[kEvSets][kEv];
   long long ev_head = 0;        // sets recorded
   long long ev_tail = 0;        // sets harvested
   bool timed = false;
-  hipEvent_t ev_done = nullptr; // end of the last batch: one of done_ev (fme_refine_status)
-  hipEvent_t ev_search = nullptr; // caller's event, recorded before each search launch (fme_set_search_event)
+  hipEvent_t ev_done = nullptr; // borrowed: end of the last batch, one of done_ev (fme_refine_status)
+  hipEvent_t ev_search = nullptr; // borrowed: the caller's event, recorded before each search launch (fme_set_search_event)
   int search_reserve = 0;         // resident search workgroups left free (fme_set_search_reserve)
   bool main10_px = false;         // bit depth 10: the pixel kernel instead of the lane kernel
                                   // (environment FME_MAIN10_SEARCH=px, an A/B switch)
@@ -306,10 +360,23 @@ struct fme_ctx {
   int acc_batches = 0;
 
   // auxiliary streams of the integer search (created on first use)
-  hipStream_t aux = nullptr;
-  hipStream_t aux2 = nullptr;
-  hipEvent_t ev_join2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  fme::Stream aux, aux2;
+  fme::Event ev_fork, ev_join, ev_join2;
+
+  // What no member frees by itself: the owned picture planes and the pinned blocks.  Everything else
+  // is a Buf, an Event or a Stream.  (fme_destroy has idled the device; fme_create's failure path
+  // comes here with whatever it had reserved.)
+  fme_ctx() = default;
+  fme_ctx(const fme_ctx&) = delete;
+  fme_ctx& operator=(const fme_ctx&) = delete;
+  ~fme_ctx() {
+    for (int i = 0; i < FME_MAX_PICTURES; i++) {
+      if (pic_owned[i] && pics[i].luma) (void)hipFree(const_cast<uint8_t*>(pics[i].luma));
+      if (chroma_owned[i]) (void)hipFree(chroma_owned[i]);
+    }
+    for (void* h : {(void*)h_counts, (void*)h_tab, (void*)stage, (void*)box})
+      if (h) (void)hipHostFree(h);
+  }
 };
 
 namespace fme {
@@ -334,4 +401,19 @@ int direct_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, fme_mv_re
 int tz_run(fme_ctx* c, fme_job* d_jobs, const fme_tz_ext* d_ext, uint32_t* d_sad, int n, void* stream, int16_t* d_emi,
            uint32_t* d_nn_in = nullptr, int ext_stride = (int)sizeof(fme_tz_ext));
 int check_rejected(fme_ctx* c, hipStream_t s, const char* name, const char* what);
+
+// The readers of a side launch's timer and counter, by member: they check the context first.
+// "<name>: null argument", "<name>: no profiled <what>"; the elapsed time of the last profiled launch
+int timer_last_ms(fme_ctx* c, LaunchTimer fme_ctx::*timer, const char* name, const char* what, float* ms);
+// "<name>: null ctx"; 0 before any launch; else waits (for the stream of the last launch, or with
+// drain_all for every stream the context used) and returns the word
+int invalid_count(fme_ctx* c, InvalidCounter fme_ctx::*counter, const char* name, bool drain_all = false);
+
+// The host checks' form of the prediction kernels' task validators (mc_job_valid, pe_task_valid,
+// sse_task_valid): PU shape, list flags, original picture, position, reference pictures.  The
+// kind sets the flag mask, whether an original picture is named (motion compensation: width x
+// height given), whether chroma planes are needed, and the texts.
+enum PredKind { kPredMc, kPredErr, kPredSse };
+const char* pred_task_problem(const fme_ctx* c, PredKind kind, int x, int y, int w, int h, unsigned flags,
+                              const uint8_t* ref_id, unsigned org_id, int width, int height);
 }  // namespace fme

@@ -10,44 +10,23 @@ namespace {
 
 // The host checks' form of k_pred_err's pe_task_valid.
 const char* pe_task_problem(const fme_ctx* c, const fme_pe_task& t) {
-  if (t.w < 4 || t.h < 4 || t.w > 64 || t.h > 64 || (t.w & 3) || (t.h & 3)) return "PU size";
-  if (!(t.flags & (FME_MC_L0 | FME_MC_L1)) || (t.flags & ~(FME_MC_L0 | FME_MC_L1 | FME_PE_LOSSLESS))) return "list flags";
-  if (t.org_id >= FME_MAX_PICTURES || !c->pics[t.org_id].luma) return "original picture";
-  const PicDesc& o = c->pics[t.org_id];
-  if ((int)t.x + t.w > o.width || (int)t.y + t.h > o.height) return "PU outside the picture";
-  for (int l = 0; l < 2; l++) {
-    if (!(t.flags & (1u << l))) continue;
-    if (t.ref_id[l] >= FME_MAX_PICTURES || !c->pics[t.ref_id[l]].luma) return "reference picture";
-    const PicDesc& p = c->pics[t.ref_id[l]];
-    if (p.width != o.width || p.height != o.height) return "reference picture dimensions";
-  }
-  return nullptr;
+  return pred_task_problem(c, kPredErr, t.x, t.y, t.w, t.h, t.flags, t.ref_id, t.org_id, 0, 0);
 }
 
 int pe_launch(fme_ctx* c, const fme_pe_task* d_tasks, uint32_t* d_dist, int n, hipStream_t s) {
-  HIP_TRY(c->d_pe_invalid.reserve(1));
-  HIP_TRY(hipMemsetAsync(c->d_pe_invalid.p, 0, sizeof(int32_t), s));
+  FME_TRY(c->pe_invalid.zero(s));
   FME_TRY(sync_tables(c, s));
-  c->pe_stream = s;
   PeArgs a{};
   a.tasks = d_tasks;
   a.pics = c->d_pics.p;
   a.dist = d_dist;
-  a.invalid = c->d_pe_invalid.p;
+  a.invalid = c->pe_invalid.d.p;
   a.n = n;
   a.bit_depth = c->cfg.bit_depth;
   a.use_hadamard = c->cfg.use_hadamard ? 1 : 0;
-  if (c->profiling) {
-    if (!c->ev_pe[0]) {
-      HIP_TRY(hipEventCreate(&c->ev_pe[0]));
-      HIP_TRY(hipEventCreate(&c->ev_pe[1]));
-    }
-    HIP_TRY(hipEventRecord(c->ev_pe[0], s));
-  }
+  FME_TRY(c->pe_timer.begin(c, s));
   HIP_TRY(launch_pred_err(a, s));
-  if (c->profiling) HIP_TRY(hipEventRecord(c->ev_pe[1], s));
-  c->pe_timed = c->profiling;
-  return FME_OK;
+  return c->pe_timer.end(c, s);
 }
 
 // Validated host tasks -> their distortions: one upload, one launch, one download, one wait.
@@ -81,21 +60,11 @@ int fme_pred_error_device(fme_ctx* c, const fme_pe_task* d_tasks, uint32_t* d_di
 }
 
 int fme_pred_error_invalid_count(fme_ctx* c) {
-  if (!c) return fail(FME_E_INVALID, "fme_pred_error_invalid_count: null ctx");
-  if (!c->d_pe_invalid.p) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  int32_t v = 0;
-  HIP_TRY(hipStreamSynchronize(c->pe_stream));   // the stream of the last launch
-  HIP_TRY(hipMemcpy(&v, c->d_pe_invalid.p, sizeof(v), hipMemcpyDeviceToHost));
-  return v;
+  return invalid_count(c, &fme_ctx::pe_invalid, "fme_pred_error_invalid_count");
 }
 
 int fme_pred_error_last_ms(fme_ctx* c, float* ms) {
-  if (!c || !ms) return fail(FME_E_INVALID, "fme_pred_error_last_ms: null argument");
-  if (!c->pe_timed) return fail(FME_E_STATE, "fme_pred_error_last_ms: no profiled prediction-error launch");
-  HIP_TRY(hipEventSynchronize(c->ev_pe[1]));
-  HIP_TRY(hipEventElapsedTime(ms, c->ev_pe[0], c->ev_pe[1]));
-  return FME_OK;
+  return timer_last_ms(c, &fme_ctx::pe_timer, "fme_pred_error_last_ms", "prediction-error launch", ms);
 }
 
 int fme_merge_estimate(fme_ctx* c, const fme_merge_req* reqs, fme_merge_res* res, int n, void* stream) {

@@ -11,45 +11,22 @@ namespace {
 
 // The host checks' form of k_pred_sse's sse_task_valid.
 const char* sse_task_problem(const fme_ctx* c, const fme_sse_task& t) {
-  if (t.w < 4 || t.h < 4 || t.w > 64 || t.h > 64 || (t.w & 3) || (t.h & 3)) return "block size";
-  if (!(t.flags & (FME_MC_L0 | FME_MC_L1)) || (t.flags & ~(FME_MC_L0 | FME_MC_L1))) return "list flags";
-  if (t.org_id >= FME_MAX_PICTURES || !c->pics[t.org_id].luma) return "original picture";
-  const PicDesc& o = c->pics[t.org_id];
-  if (!o.cb || !o.cr) return "original picture without chroma planes";
-  if ((int)t.x + t.w > o.width || (int)t.y + t.h > o.height) return "block outside the picture";
-  for (int l = 0; l < 2; l++) {
-    if (!(t.flags & (1u << l))) continue;
-    if (t.ref_id[l] >= FME_MAX_PICTURES || !c->pics[t.ref_id[l]].luma) return "reference picture";
-    const PicDesc& p = c->pics[t.ref_id[l]];
-    if (!p.cb || !p.cr) return "reference picture without chroma planes";
-    if (p.width != o.width || p.height != o.height) return "reference picture dimensions";
-  }
-  return nullptr;
+  return pred_task_problem(c, kPredSse, t.x, t.y, t.w, t.h, t.flags, t.ref_id, t.org_id, 0, 0);
 }
 
 int sse_launch(fme_ctx* c, const fme_sse_task* d_tasks, uint32_t* d_sse, int n, hipStream_t s) {
-  HIP_TRY(c->d_sse_invalid.reserve(1));
-  HIP_TRY(hipMemsetAsync(c->d_sse_invalid.p, 0, sizeof(int32_t), s));
+  FME_TRY(c->sse_invalid.zero(s));
   FME_TRY(sync_tables(c, s));
-  c->sse_stream = s;
   SseArgs a{};
   a.tasks = d_tasks;
   a.pics = c->d_pics.p;
   a.sse = d_sse;
-  a.invalid = c->d_sse_invalid.p;
+  a.invalid = c->sse_invalid.d.p;
   a.n = n;
   a.bit_depth = c->cfg.bit_depth;
-  if (c->profiling) {
-    if (!c->ev_sse[0]) {
-      HIP_TRY(hipEventCreate(&c->ev_sse[0]));
-      HIP_TRY(hipEventCreate(&c->ev_sse[1]));
-    }
-    HIP_TRY(hipEventRecord(c->ev_sse[0], s));
-  }
+  FME_TRY(c->sse_timer.begin(c, s));
   HIP_TRY(launch_pred_sse(a, s));
-  if (c->profiling) HIP_TRY(hipEventRecord(c->ev_sse[1], s));
-  c->sse_timed = c->profiling;
-  return FME_OK;
+  return c->sse_timer.end(c, s);
 }
 
 // Validated host tasks -> their SSEs: one upload, one launch, one download, one wait.
@@ -83,21 +60,11 @@ int fme_pred_sse_device(fme_ctx* c, const fme_sse_task* d_tasks, uint32_t (*d_ss
 }
 
 int fme_pred_sse_invalid_count(fme_ctx* c) {
-  if (!c) return fail(FME_E_INVALID, "fme_pred_sse_invalid_count: null ctx");
-  if (!c->d_sse_invalid.p) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  int32_t v = 0;
-  HIP_TRY(hipStreamSynchronize(c->sse_stream));   // the stream of the last launch
-  HIP_TRY(hipMemcpy(&v, c->d_sse_invalid.p, sizeof(v), hipMemcpyDeviceToHost));
-  return v;
+  return invalid_count(c, &fme_ctx::sse_invalid, "fme_pred_sse_invalid_count");
 }
 
 int fme_pred_sse_last_ms(fme_ctx* c, float* ms) {
-  if (!c || !ms) return fail(FME_E_INVALID, "fme_pred_sse_last_ms: null argument");
-  if (!c->sse_timed) return fail(FME_E_STATE, "fme_pred_sse_last_ms: no profiled SSE launch");
-  HIP_TRY(hipEventSynchronize(c->ev_sse[1]));
-  HIP_TRY(hipEventElapsedTime(ms, c->ev_sse[0], c->ev_sse[1]));
-  return FME_OK;
+  return timer_last_ms(c, &fme_ctx::sse_timer, "fme_pred_sse_last_ms", "SSE launch", ms);
 }
 
 int fme_skip_estimate(fme_ctx* c, const fme_skip_params* params, const fme_skip_req* reqs, fme_skip_res* res, int n,

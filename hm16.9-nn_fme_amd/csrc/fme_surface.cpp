@@ -26,10 +26,8 @@ const char* surf_job_problem(const fme_ctx* c, const fme_job& j, const uint8_t* 
 
 int surf_launch(fme_ctx* c, const fme_job* d_jobs, const uint8_t* d_probe, fme_surface* d_surf, fme_surface_pick* d_pick,
                 int n, hipStream_t s) {
-  HIP_TRY(c->d_surf_invalid.reserve(1));
-  HIP_TRY(hipMemsetAsync(c->d_surf_invalid.p, 0, sizeof(int32_t), s));
+  FME_TRY(c->surf_invalid.zero(s));
   FME_TRY(sync_tables(c, s));
-  c->surf_stream = s;
   SurfArgs a{};
   a.jobs = d_jobs;
   a.probe = d_probe;
@@ -39,21 +37,13 @@ int surf_launch(fme_ctx* c, const fme_job* d_jobs, const uint8_t* d_probe, fme_s
   a.mlambda = c->d_mlambda.p;
   a.keys = c->d_keys.p;
   a.n_keys = (int64_t)c->n_keys;
-  a.invalid = c->d_surf_invalid.p;
+  a.invalid = c->surf_invalid.d.p;
   a.n = n;
   a.bit_depth = c->cfg.bit_depth;
   a.use_hadamard = c->cfg.use_hadamard ? 1 : 0;
-  if (c->profiling) {
-    if (!c->ev_surf[0]) {
-      HIP_TRY(hipEventCreate(&c->ev_surf[0]));
-      HIP_TRY(hipEventCreate(&c->ev_surf[1]));
-    }
-    HIP_TRY(hipEventRecord(c->ev_surf[0], s));
-  }
+  FME_TRY(c->surf_timer.begin(c, s));
   HIP_TRY(launch_cost_surface(a, s));
-  if (c->profiling) HIP_TRY(hipEventRecord(c->ev_surf[1], s));
-  c->surf_timed = c->profiling;
-  return FME_OK;
+  return c->surf_timer.end(c, s);
 }
 
 }  // namespace
@@ -93,21 +83,11 @@ int fme_cost_surface_device(fme_ctx* c, const fme_job* d_jobs, const uint8_t (*d
 }
 
 int fme_cost_surface_invalid_count(fme_ctx* c) {
-  if (!c) return fail(FME_E_INVALID, "fme_cost_surface_invalid_count: null ctx");
-  if (!c->d_surf_invalid.p) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  int32_t v = 0;
-  HIP_TRY(hipStreamSynchronize(c->surf_stream));   // the stream of the last launch
-  HIP_TRY(hipMemcpy(&v, c->d_surf_invalid.p, sizeof(v), hipMemcpyDeviceToHost));
-  return v;
+  return invalid_count(c, &fme_ctx::surf_invalid, "fme_cost_surface_invalid_count");
 }
 
 int fme_cost_surface_last_ms(fme_ctx* c, float* ms) {
-  if (!c || !ms) return fail(FME_E_INVALID, "fme_cost_surface_last_ms: null argument");
-  if (!c->surf_timed) return fail(FME_E_STATE, "fme_cost_surface_last_ms: no profiled surface launch");
-  HIP_TRY(hipEventSynchronize(c->ev_surf[1]));
-  HIP_TRY(hipEventElapsedTime(ms, c->ev_surf[0], c->ev_surf[1]));
-  return FME_OK;
+  return timer_last_ms(c, &fme_ctx::surf_timer, "fme_cost_surface_last_ms", "surface launch", ms);
 }
 
 }  // extern "C"
