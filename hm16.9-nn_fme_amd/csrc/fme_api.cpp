@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <memory>
 
+#include "fme_among_host.h"
 #include "fme_ctx.h"
 #include "fme_direct_host.h"
 #include "fme_extern_host.h"
@@ -1035,6 +1036,118 @@ static int extern_enter(fme_ctx* c, int rq, int n, const char* name, bool* run) 
   return FME_OK;
 }
 
+// ---- candidate-set refinement (include/fme_among.h) -----------------------------------------------
+// The among batch is at_batch with a list per job; the top-K batch is the inputs batch followed by
+// the ranking and the among evaluation inside one scaffolded batch.  Their profiling events: [0] /
+// [1] around k_front, [2] behind the EMI kernel, [3] the rows kernel, [4] the ranking, [5] the
+// evaluation.
+static int among_events(fme_ctx* c) {
+  if (c->profiling)
+    for (auto& e : c->ev_among)
+      if (!e) HIP_TRY(hipEventCreate(&e.h));
+  c->among_timed = false;   // until the call is enqueued in full
+  return FME_OK;
+}
+
+static AmongArgs among_args(const fme_ctx* c, const Batch& b, const fme_nn_row* d_rows, const uint8_t* d_cand, int k,
+                            fme_result* d_res, fme_mv_result* d_mv, uint32_t* d_cost, bool topk) {
+  AmongArgs x{};
+  x.d = direct_args(c, b);
+  x.d.a.res = d_res;
+  x.d.mv_out = d_mv;
+  x.rows = d_rows;
+  x.cand = d_cand;
+  x.cand_cost = d_cost;
+  x.refused = c->d_am_refused.p;
+  x.k = k;
+  x.status = FME_RES_NN_DIRECT | FME_RES_NN_AMONG | (topk ? 0u : FME_RES_NN_EXTERN);
+  x.row_status = topk ? 1 : 0;
+  x.n = b.a.n;
+  x.bit_depth = c->cfg.bit_depth;
+  return x;
+}
+
+// k_front -> EMI kernel unless the caller brought rows -> evaluation over the caller's lists.  d_res:
+// the full records (with d_mv and no rows: context-internal ones the EMI kernel writes; with d_mv and
+// rows: null).  The NN state is not touched.
+static int among_batch(fme_ctx* c, const fme_job* d_jobs, const fme_nn_row* d_rows, const uint8_t* d_cand, int k,
+                       fme_result* d_res, fme_mv_result* d_mv, uint32_t* d_cost, int n, hipStream_t s) {
+  HIP_TRY(c->d_am_refused.reserve(1));
+  const bool prof = c->profiling;
+  const Event* ev = c->ev_among;
+  FME_TRY(among_events(c));
+  Batch b;
+  FME_TRY(batch_begin(c, d_jobs, nullptr, nullptr, d_res, n, s, kOvForeign, 1, c->d_am_refused.p,
+                      prof ? ev[0] : nullptr, prof ? ev[1] : nullptr, &b));
+  if (!d_rows) {
+    HIP_TRY(launch_direct_emi(direct_args(c, b), s));
+    if (prof) HIP_TRY(hipEventRecord(ev[2], s));
+  }
+  HIP_TRY(hipEventRecord(b.search_end, s));
+  HIP_TRY(launch_among_eval(among_args(c, b, d_rows, d_cand, k, d_res, d_mv, d_cost, false), s));
+  if (prof) HIP_TRY(hipEventRecord(ev[5], s));
+  c->among_phases = d_rows ? 8u : 9u;
+  c->among_timed = prof;
+  FME_TRY(batch_end(c, s, b, false));
+  c->ev_among_done = b.done;
+  return FME_OK;
+}
+
+// The context's rows and candidates of a top-K batch: sized for max_jobs on first use.
+static int topk_buffers(fme_ctx* c, int n, int k, bool own_cand) {
+  const size_t cap = std::max<size_t>((size_t)n, (size_t)std::max(c->cfg.max_jobs, 0));
+  HIP_TRY(c->d_am_rows.reserve(cap));
+  if (own_cand) HIP_TRY(c->d_am_cand.reserve(cap * FME_AMONG_MAX));
+  (void)k;
+  return FME_OK;
+}
+
+// k_front -> EMI kernel (on d_rec, context-internal records) -> rows kernel (the NN state handed on
+// as by the inputs batch) -> ranking -> evaluation with the rows into d_res / d_mv.
+static int topk_batch(fme_ctx* c, const fme_job* d_jobs, fme_result* d_rec, fme_result* d_res, fme_mv_result* d_mv,
+                      int k, uint8_t* d_cand, uint32_t* d_cost, int n, hipStream_t s) {
+  HIP_TRY(c->d_am_refused.reserve(1));
+  FME_TRY(topk_buffers(c, n, k, !d_cand));
+  if (!d_cand) d_cand = c->d_am_cand.p;
+  fme_nn_row* const d_rows = c->d_am_rows.p;
+  const bool prof = c->profiling;
+  const Event* ev = c->ev_among;
+  FME_TRY(among_events(c));
+  Batch b;
+  FME_TRY(batch_begin(c, d_jobs, nullptr, nullptr, d_rec, n, s, kOvForeign, 1, c->d_am_refused.p,
+                      prof ? ev[0] : nullptr, prof ? ev[1] : nullptr, &b));
+  HIP_TRY(launch_direct_emi(direct_args(c, b), s));
+  if (prof) HIP_TRY(hipEventRecord(ev[2], s));
+  HIP_TRY(hipEventRecord(b.search_end, s));
+  FME_TRY(hand_state_on(c, s, b));
+  HIP_TRY(launch_nn_rows(b.a, b.w, d_rows, c->state_cur, false, s));
+  if (prof) HIP_TRY(hipEventRecord(ev[3], s));
+  HIP_TRY(launch_nn_rank(d_rows, c->d_nn.p, d_cand, k, n, s));
+  if (prof) HIP_TRY(hipEventRecord(ev[4], s));
+  HIP_TRY(launch_among_eval(among_args(c, b, d_rows, d_cand, k, d_res, d_mv, d_cost, true), s));
+  if (prof) HIP_TRY(hipEventRecord(ev[5], s));
+  c->among_phases = 15u;
+  c->among_timed = prof;
+  FME_TRY(batch_end(c, s, b, true));
+  c->ev_among_done = b.done;
+  return FME_OK;
+}
+
+// The families' common start: the argument check (fme_among_host.h); *run: enqueue.
+static int among_enter(fme_ctx* c, int rq, int k, int n, const char* name, bool* run) {
+  *run = false;
+  if (rq == FME_E_STATE && c->nn_in)
+    return fail(rq, "%s: NN input rows are bound (fme_set_nn_inputs): the inputs are the caller's", name);
+  if (rq == FME_E_STATE) return fail(rq, "%s: needs nn_mode 1 with weights loaded", name);
+  if (rq == FME_E_UNSUPPORTED) return fail(rq, "%s: the two-layer net only (nn_mode 1), not nn_mode 2", name);
+  if (rq < 0) return fail(rq, "%s: bad argument (k = %d, n = %d)", name, k, n);
+  if (rq == 0) {
+    HIP_TRY(hipSetDevice(c->device));
+    *run = true;
+  }
+  return FME_OK;
+}
+
 extern "C" {
 
 int fme_nn_inputs(fme_ctx* c, const fme_job* jobs, fme_nn_row* rows, int n, void* stream) {
@@ -1121,6 +1234,140 @@ int fme_extern_last_ms(fme_ctx* c, float ms[4]) {
   if (ph & 2u) HIP_TRY(hipEventElapsedTime(&ms[1], e[2], e[3]));
   if (ph & 4u) HIP_TRY(hipEventElapsedTime(&ms[2], e[(ph & 1u) ? 2 : 1], e[4]));
   HIP_TRY(hipEventElapsedTime(&ms[3], e[0], e[last]));
+  return FME_OK;
+}
+
+int fme_refine_among(fme_ctx* c, const fme_job* jobs, const fme_nn_row* rows, const uint8_t* cand, int k, fme_result* res,
+                     uint32_t* cand_cost, int n, void* stream) {
+  bool run;
+  FME_TRY(among_enter(c, among_request(c, jobs, cand, k, res, n, c && c->nn_in), k, n, "fme_refine_among", &run));
+  if (!run) return FME_OK;
+  const int bad = among_first_refused(jobs, rows, cand, k, n);
+  if (bad >= 0)
+    return fail(FME_E_INVALID, "fme_refine_among: job %d has %s", bad,
+                among_list_ok(cand + (size_t)bad * k, k) ? "a row that is not its own"
+                                                         : "a list with a slot in 49..254 or no class at all");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t nk = (size_t)n * k;
+  HIP_TRY(c->d_jobs.reserve(n));
+  HIP_TRY(c->d_res.reserve(n));
+  HIP_TRY(c->d_am_cand.reserve(nk));
+  if (rows) HIP_TRY(c->d_am_rows.reserve(n));
+  if (cand_cost) HIP_TRY(c->d_am_cost.reserve(nk));
+  HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, (size_t)n * sizeof(fme_job), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->d_am_cand.p, cand, nk, hipMemcpyHostToDevice, s));
+  if (rows) HIP_TRY(hipMemcpyAsync(c->d_am_rows.p, rows, (size_t)n * sizeof(fme_nn_row), hipMemcpyHostToDevice, s));
+  FME_TRY(among_batch(c, c->d_jobs.p, rows ? c->d_am_rows.p : nullptr, c->d_am_cand.p, k, c->d_res.p, nullptr,
+                      cand_cost ? c->d_am_cost.p : nullptr, n, s));
+  // the rejected-job count first: an invalid batch leaves the caller's arrays as they were
+  FME_TRY(check_rejected(c, s, "fme_refine_among", "with an unsupported PU size or unset picture/lambda/key"));
+  HIP_TRY(hipMemcpy(res, c->d_res.p, (size_t)n * sizeof(fme_result), hipMemcpyDeviceToHost));
+  if (cand_cost) HIP_TRY(hipMemcpy(cand_cost, c->d_am_cost.p, nk * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return FME_OK;
+}
+
+int fme_refine_among_device(fme_ctx* c, const fme_job* d_jobs, const fme_nn_row* d_rows, const uint8_t* d_cand, int k,
+                            fme_result* d_res, uint32_t* d_cand_cost, int n, void* stream) {
+  bool run;
+  FME_TRY(among_enter(c, among_request(c, d_jobs, d_cand, k, d_res, n, c && c->nn_in), k, n, "fme_refine_among_device", &run));
+  return run ? among_batch(c, d_jobs, d_rows, d_cand, k, d_res, nullptr, d_cand_cost, n, static_cast<hipStream_t>(stream))
+             : FME_OK;
+}
+
+int fme_refine_among_mv_device(fme_ctx* c, const fme_job* d_jobs, const fme_nn_row* d_rows, const uint8_t* d_cand, int k,
+                               fme_mv_result* d_out, uint32_t* d_cand_cost, int n, void* stream) {
+  bool run;
+  FME_TRY(among_enter(c, among_request(c, d_jobs, d_cand, k, d_out, n, c && c->nn_in), k, n, "fme_refine_among_mv_device", &run));
+  if (!run) return FME_OK;
+  fme_result* d_rec = nullptr;   // the EMI kernel's records; with rows nothing reads or writes them
+  if (!d_rows) FME_TRY(slot_records(c, n, &d_rec));
+  return among_batch(c, d_jobs, d_rows, d_cand, k, d_rec, d_out, d_cand_cost, n, static_cast<hipStream_t>(stream));
+}
+
+int fme_refine_among_status(fme_ctx* c) {
+  if (!c) return fail(FME_E_INVALID, "fme_refine_among_status: null ctx");
+  if (!c->ev_among_done) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->ev_among_done));
+  int32_t v = 0;
+  HIP_TRY(hipMemcpy(&v, c->d_am_refused.p, sizeof(v), hipMemcpyDeviceToHost));
+  return v;
+}
+
+int fme_nn_rank_device(fme_ctx* c, const fme_nn_row* d_rows, uint8_t* d_cand, int k, int n, void* stream) {
+  bool run;
+  FME_TRY(among_enter(c, among_rank_request(c, d_rows, d_cand, k, n, c ? c->cfg.nn_mode : 1, c && c->nn_loaded), k, n,
+                      "fme_nn_rank_device", &run));
+  if (!run) return FME_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool prof = c->profiling;
+  const Event* ev = c->ev_among;
+  FME_TRY(among_events(c));
+  if (prof) HIP_TRY(hipEventRecord(ev[0], s));
+  HIP_TRY(launch_nn_rank(d_rows, c->d_nn.p, d_cand, k, n, s));
+  if (prof) HIP_TRY(hipEventRecord(ev[4], s));
+  c->among_phases = 4u;
+  c->among_timed = prof;
+  return FME_OK;
+}
+
+int fme_refine_topk(fme_ctx* c, const fme_job* jobs, fme_result* res, int k, uint8_t* cand, uint32_t* cand_cost, int n,
+                    void* stream) {
+  bool run;
+  FME_TRY(among_enter(c, among_topk_request(c, jobs, res, k, n, c && c->nn_in, c ? c->cfg.nn_mode : 1, c && c->nn_loaded), k,
+                      n, "fme_refine_topk", &run));
+  if (!run) return FME_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t nk = (size_t)n * k;
+  HIP_TRY(c->d_jobs.reserve(n));
+  HIP_TRY(c->d_res.reserve(n));
+  if (cand_cost) HIP_TRY(c->d_am_cost.reserve(nk));
+  HIP_TRY(hipMemcpyAsync(c->d_jobs.p, jobs, (size_t)n * sizeof(fme_job), hipMemcpyHostToDevice, s));
+  // the EMI kernel's records and the batch's own share c->d_res: the evaluation writes whole records
+  // behind the rows kernel, the one reader of the EMI kernel's
+  FME_TRY(topk_batch(c, c->d_jobs.p, c->d_res.p, c->d_res.p, nullptr, k, nullptr, cand_cost ? c->d_am_cost.p : nullptr, n, s));
+  FME_TRY(check_rejected(c, s, "fme_refine_topk", "with an unsupported PU size or unset picture/lambda/key"));
+  HIP_TRY(hipMemcpy(res, c->d_res.p, (size_t)n * sizeof(fme_result), hipMemcpyDeviceToHost));
+  if (cand) HIP_TRY(hipMemcpy(cand, c->d_am_cand.p, nk, hipMemcpyDeviceToHost));
+  if (cand_cost) HIP_TRY(hipMemcpy(cand_cost, c->d_am_cost.p, nk * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return FME_OK;
+}
+
+int fme_refine_topk_device(fme_ctx* c, const fme_job* d_jobs, fme_result* d_res, int k, uint8_t* d_cand,
+                           uint32_t* d_cand_cost, int n, void* stream) {
+  bool run;
+  FME_TRY(among_enter(c, among_topk_request(c, d_jobs, d_res, k, n, c && c->nn_in, c ? c->cfg.nn_mode : 1, c && c->nn_loaded),
+                      k, n, "fme_refine_topk_device", &run));
+  // (the EMI kernel writes the caller's records, the evaluation overwrites them whole)
+  return run ? topk_batch(c, d_jobs, d_res, d_res, nullptr, k, d_cand, d_cand_cost, n, static_cast<hipStream_t>(stream))
+             : FME_OK;
+}
+
+int fme_refine_topk_mv_device(fme_ctx* c, const fme_job* d_jobs, fme_mv_result* d_out, int k, uint8_t* d_cand,
+                              uint32_t* d_cand_cost, int n, void* stream) {
+  bool run;
+  FME_TRY(among_enter(c, among_topk_request(c, d_jobs, d_out, k, n, c && c->nn_in, c ? c->cfg.nn_mode : 1, c && c->nn_loaded),
+                      k, n, "fme_refine_topk_mv_device", &run));
+  if (!run) return FME_OK;
+  fme_result* d_rec = nullptr;
+  FME_TRY(slot_records(c, n, &d_rec));
+  return topk_batch(c, d_jobs, d_rec, nullptr, d_out, k, d_cand, d_cand_cost, n, static_cast<hipStream_t>(stream));
+}
+
+int fme_among_last_ms(fme_ctx* c, float ms[5]) {
+  if (!c || !ms) return fail(FME_E_INVALID, "fme_among_last_ms: null argument");
+  if (!c->among_timed) return fail(FME_E_STATE, "fme_among_last_ms: no profiled among / rank / top-K call");
+  HIP_TRY(hipSetDevice(c->device));
+  const Event* e = c->ev_among;
+  const unsigned ph = c->among_phases;
+  const int last = (ph & 8u) ? 5 : 4;
+  HIP_TRY(hipEventSynchronize(e[last]));
+  ms[0] = ms[1] = ms[2] = ms[3] = 0.f;
+  if (ph & 1u) HIP_TRY(hipEventElapsedTime(&ms[0], e[1], e[2]));
+  if (ph & 2u) HIP_TRY(hipEventElapsedTime(&ms[1], e[2], e[3]));
+  if (ph & 4u) HIP_TRY(hipEventElapsedTime(&ms[2], e[(ph & 2u) ? 3 : 0], e[4]));
+  if (ph & 8u) HIP_TRY(hipEventElapsedTime(&ms[3], e[(ph & 4u) ? 4 : (ph & 1u) ? 2 : 1], e[5]));
+  HIP_TRY(hipEventElapsedTime(&ms[4], e[0], e[last]));
   return FME_OK;
 }
 

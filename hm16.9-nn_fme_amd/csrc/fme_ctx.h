@@ -272,6 +272,19 @@ struct fme_ctx {
   fme::Event ev_extern[5];
   unsigned extern_phases = 0;
   bool extern_timed = false;
+  // candidate-set refinement (include/fme_among.h): the top-K batch's rows and candidates (sized for
+  // max_jobs on first use), staging of the host forms' lists, rows and costs, the count of the jobs
+  // the last among / top-K batch refused one by one and that batch's end event (one of done_ev), and
+  // the timing events of the last call with profiling on: start, front end, EMI, rows, rank and
+  // evaluation kernel ends (among_phases: bit 0 EMI, 1 rows, 2 rank, 3 evaluation ran)
+  fme::DevBuf<fme_nn_row> d_am_rows;
+  fme::DevBuf<uint8_t> d_am_cand;
+  fme::DevBuf<uint32_t> d_am_cost;
+  fme::DevBuf<int32_t> d_am_refused;
+  hipEvent_t ev_among_done = nullptr;   // borrowed: one of done_ev
+  fme::Event ev_among[6];
+  unsigned among_phases = 0;
+  bool among_timed = false;
   // integer search: staging for the host entry point, the timer
   fme::DevBuf<fme_tz_ext> d_tz_ext;
   fme::DevBuf<uint32_t> d_tz_sad;

@@ -288,6 +288,24 @@ hipError_t launch_at_eval(const ExternArgs& x, hipStream_t s);
 hipError_t launch_nn_rows(const BatchArgs& a, const WorkBufs& w, fme_nn_row* rows, int state_in, bool slot_reset,
                           hipStream_t s);
 
+// Candidate-set refinement's two kernels (fme_among.hip, include/fme_among.h).
+struct AmongArgs {
+  DirectArgs d;               // d.a.res: the records (null with rows and the compact output)
+  const fme_nn_row* rows;     // the jobs' NN input rows, or null: the EMI kernel wrote the records
+  const uint8_t* cand;        // [n][k] candidate classes, FME_AMONG_EMPTY: an unused slot
+  uint32_t* cand_cost;        // [n][k] the slots' costs, or null
+  int32_t* refused;           // count of the jobs refused one by one (zeroed before the launch)
+  int32_t k;                  // 1..FME_AMONG_MAX
+  uint32_t status;            // the records' status bits
+  int32_t row_status;         // 1: and the row's FME_RES_NN_STALE / _UNINIT (the top-K batch)
+  int32_t n;
+  int32_t bit_depth;
+};
+// per job the sub-pel evaluation at every class of its list and the record of the first least
+hipError_t launch_among_eval(const AmongArgs& x, hipStream_t s);
+// per row the k classes the two-layer net (nn_pack's layout) rates highest, best first
+hipError_t launch_nn_rank(const fme_nn_row* rows, const float* nn_params, uint8_t* cand, int k, int n, hipStream_t s);
+
 // What the schedule needs to know about the search kernel: lanes per PU of each class (its unit
 // count rounded up to a power of two).
 struct SchedParams {

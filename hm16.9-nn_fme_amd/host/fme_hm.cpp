@@ -73,6 +73,11 @@ std::vector<float> loadWeights(const std::string& dir_in, int qp) {
 FracSearch::FracSearch(const SearchConfig& cfg) : cfg_(cfg) {
   if (cfg.nnDirect && cfg.nnMode == 0)
     throw Error(FME_E_STATE, "SearchConfig::nnDirect needs nnMode != 0: there is no class to evaluate");
+  if (cfg.nnTopK < 0 || cfg.nnTopK > FME_AMONG_MAX || (cfg.nnTopK && !cfg.nnDirect))
+    throw Error(FME_E_INVALID, "SearchConfig::nnTopK is 0 (off) or 1..8, and only with nnDirect");
+  if (cfg.nnTopK && cfg.nnMode != 1)
+    throw Error(cfg.nnMode == 2 ? FME_E_UNSUPPORTED : FME_E_STATE,
+                "SearchConfig::nnTopK ranks the outputs of the two-layer net: nnMode 1");
   fme_config c{};
   c.bit_depth = cfg.bitDepth;
   c.use_hadamard = cfg.useHadamardME ? 1 : 0;
@@ -93,8 +98,13 @@ FracSearch::~FracSearch() {
 
 void FracSearch::refine(const fme_job* jobs, fme_result* results, int n) {
   std::lock_guard<std::mutex> lock(mu_);
-  check(cfg_.nnDirect ? fme_refine_direct(ctx_, jobs, results, n, nullptr) : fme_refine(ctx_, jobs, results, n, nullptr),
-        cfg_.nnDirect ? "fme_refine_direct" : "fme_refine");
+  check(refineLocked(jobs, results, n),
+        cfg_.nnTopK ? "fme_refine_topk" : cfg_.nnDirect ? "fme_refine_direct" : "fme_refine");
+}
+
+int FracSearch::refineLocked(const fme_job* jobs, fme_result* results, int n) {
+  if (cfg_.nnTopK) return fme_refine_topk(ctx_, jobs, results, cfg_.nnTopK, nullptr, nullptr, n, nullptr);
+  return cfg_.nnDirect ? fme_refine_direct(ctx_, jobs, results, n, nullptr) : fme_refine(ctx_, jobs, results, n, nullptr);
 }
 
 void FracSearch::setLambda(double lambda) { mlambda_ = 65536.0 * std::sqrt(lambda); }  // TComRdCost.cpp:104-117
@@ -450,8 +460,7 @@ void CtuRowBatcher::worker() {
       int rc = FME_OK;
       if (!r->keys.empty()) rc = fme_set_keys(c, r->keys.data(), r->keys.size(), nullptr);
       if (rc == FME_OK && !r->jobs.empty())   // (FracSearch::refine's call, under the lock already held)
-        rc = search_.nnDirect() ? fme_refine_direct(c, r->jobs.data(), r->results.data(), (int)r->jobs.size(), nullptr)
-                                : fme_refine(c, r->jobs.data(), r->results.data(), (int)r->jobs.size(), nullptr);
+        rc = search_.refineLocked(r->jobs.data(), r->results.data(), (int)r->jobs.size());
       if (rc != FME_OK) {
         r->rc = rc;
         r->err = fme_last_error();

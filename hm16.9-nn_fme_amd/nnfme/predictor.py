@@ -214,22 +214,33 @@ def features_torch(d_rows):
     return (cols.to(torch.int64) & 0xFFFFFFFF).to(torch.float32)
 
 
-def run(ctx, d_jobs, model, d_rows, d_cls, d_res, stream=None):
+def run(ctx, d_jobs, model, d_rows, d_cls, d_res, stream=None, topk=None):
     """One stream-ordered step with any torch predictor, nothing synchronised: the inputs call,
     features_torch, `model` with its argmax to uint8 into d_cls, fme_refine_at_device with the rows.
 
     d_jobs: uint8 tensor of JOB_DTYPE records; d_rows (64 n bytes), d_cls (uint8 [n]) and d_res (64 n
     bytes) are the caller's device tensors; stream: a torch.cuda.Stream (None: the current one).
     model(x) returns scores [n, 49] (their argmax is the class) or the classes [n] themselves; a model
-    with a true attribute `takes_rows` gets the rows' int32 words [n, 16] instead of the features."""
+    with a true attribute `takes_rows` gets the rows' int32 words [n, 16] instead of the features.
+
+    topk = k (1..8): the model returns scores [n, 49], d_cls is uint8 [n, k] and receives the scores'
+    topk(k) indices as each job's candidate list, and fme_refine_among_device (include/fme_among.h)
+    runs on it instead: the record is the best of the k."""
     import torch
-    n = int(d_cls.numel())
+    n = int(d_cls.numel()) if topk is None else int(d_cls.numel()) // int(topk)
     stream = torch.cuda.current_stream(d_cls.device) if stream is None else stream
     with torch.cuda.stream(stream):
         nn_inputs_device(ctx, d_jobs, d_rows, n, stream.cuda_stream)
         x = rows_torch(d_rows) if getattr(model, "takes_rows", False) else features_torch(d_rows)
         with torch.no_grad():
             y = model(x)
-        d_cls.copy_((y.argmax(dim=1) if y.dim() == 2 else y).to(torch.uint8))
-        refine_at_device(ctx, d_jobs, d_rows, d_cls, d_res, n, stream.cuda_stream)
+        if topk is None:
+            d_cls.copy_((y.argmax(dim=1) if y.dim() == 2 else y).to(torch.uint8))
+            refine_at_device(ctx, d_jobs, d_rows, d_cls, d_res, n, stream.cuda_stream)
+        else:
+            from . import among
+            if y.dim() != 2:
+                raise ValueError("run(topk=k): the model returns scores [n, 49]")
+            d_cls.view(n, int(topk)).copy_(y.topk(int(topk), dim=1).indices.to(torch.uint8))
+            among.refine_among_device(ctx, d_jobs, d_rows, d_cls, int(topk), d_res, None, n, stream.cuda_stream)
 

@@ -12,7 +12,8 @@
 //     NN_pred + tail, TEncSearch.cpp:4529-4597, 5037-5050) of one CTU row, hands the row to a
 //     worker thread that runs it on the GPU while the caller fills the next row, and returns
 //     the results in queue order (the NN's carried state follows queue order across rows).
-//     With SearchConfig::nnDirect the rows run NN-direct (include/fme_direct.h) instead.
+//     With SearchConfig::nnDirect the rows run NN-direct (include/fme_direct.h) instead, and with
+//     SearchConfig::nnTopK the best of the net's K highest classes (include/fme_among.h).
 //
 // Pel planes are HM's int16 samples; pictures are converted to the library's planes at the
 // search's bit depth (SearchConfig::bitDepth): uint8_t samples at 8 bits, uint16_t at 10 (the
@@ -34,6 +35,7 @@
 #include <vector>
 
 #include "fme.h"
+#include "fme_among.h"
 #include "fme_direct.h"
 #include "fme_merge.h"
 #include "fme_skip.h"
@@ -75,6 +77,10 @@ struct SearchConfig {
                               // cost are then the returned MV's own, which the shipped encoder never
                               // computes.  Needs nnMode != 0 (else Error, FME_E_STATE).  The single calls
                               // (xPatternSearchFracDIF, NN_pred) are as they were.
+  int nnTopK = 0;             // 0: off; 1..8: the batch path runs fme_refine_topk (include/fme_among.h): the
+                              // best of the net's nnTopK highest classes instead of its first alone.  Only
+                              // with nnDirect (else Error, FME_E_INVALID, as for a value outside 0..8) and
+                              // with the two-layer net, nnMode 1 (nnMode 0: FME_E_STATE, 2: FME_E_UNSUPPORTED).
 };
 
 // Reads weights/nn2_qp<set>.bin (2060 float64 -> float32, the set TEncSearch::init picks).
@@ -115,11 +121,14 @@ class FracSearch {
   void setLambdaSlot(int lambdaId, double lambda);
 
   // The batch path: n sub-pel jobs in call order, synchronous, under mutex(): fme_refine, or with
-  // SearchConfig::nnDirect fme_refine_direct.  CtuRowBatcher's rows run through it.
+  // SearchConfig::nnDirect fme_refine_direct, or with nnTopK as well fme_refine_topk.  CtuRowBatcher's
+  // rows run through refineLocked, under the lock they hold already.
   void refine(const fme_job* jobs, fme_result* results, int n);
+  int refineLocked(const fme_job* jobs, fme_result* results, int n);   // the library's return code
 
   int bitDepth() const { return cfg_.bitDepth; }
   bool nnDirect() const { return cfg_.nnDirect; }
+  int nnTopK() const { return cfg_.nnTopK; }
   fme_ctx* ctx() const { return ctx_; }
   std::mutex& mutex() { return mu_; }   // serialises context use with a running batcher
 
